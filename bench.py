@@ -10,11 +10,22 @@ timed region.  Workload (BASELINE.json metric / configs[2]): UNet channels [64,1
 512x512 1-channel, batch 32 per GPU, bf16 activations / MFMA operands with fp32 accumulation,
 statistics, parameters, logits and loss.  Weak scaling: per-GPU batch is fixed.
 
-One JSON line on rank 0 with `roofline` = the canonical full-resolution C0 -> C0 PlainBlock: conv launch +
-statistics finalize + normalise/LeakyReLU apply, each timed live with HIP events on the launch stream, priced against its
-algorithmic bytes (read x once, write z once); the conv launch alone is the sub-record `roofline.conv`.  `cpu_baseline` =
-the oracle's train step (oracle/train_ref.py, a port of the reference loop validated against the reference) on the host
-cores: 2 warm-ups, median of 5 (SURVEY 8d protocol).  `parity` = the benchmarked widths and dtype against the fp32 oracle.
+A plain run sets up, warms up, times `--steps` steps and prints one JSON line on rank 0 (`value` images/sec, `ms_per_step`).
+The warm-up is `--warmup` steps plus SETTLE_STEPS more (the engine's auto graph mode decides within them), so the number of
+steps before the timed region does not depend on timing and the same arguments give the same computation run after run.
+
+--dump-outputs DIR: after the timed steps, what the last one computed as a caller of `TrainEngine.train_step` receives it --
+the loss (`loss.npy`) and the model state after the step (`state.<state_dict key>.npy`, float32; tensors above
+DUMP_SAMPLE elements as a fixed, seeded sample of their flattened elements) -- at most DUMP_BUDGET bytes in all.
+
+--full adds everything beyond the headline figure, outside the timed region unless said otherwise.  `roofline` = the canonical
+full-resolution C0 -> C0 PlainBlock: conv launch + statistics finalize + normalise/LeakyReLU apply, each timed live
+with HIP events on the launch stream inside the timed region, priced against its algorithmic bytes (read x once, write z once);
+the conv launch alone is the sub-record `roofline.conv`.  `value_host_fed` = the same steps fed from host memory;
+`value_without_augmentation` (augmenting configs) = the steps on a fixed, already augmented batch.  `cpu_baseline` = the
+oracle's train step (oracle/train_ref.py, a port of the reference loop validated against the reference) on the host cores:
+2 warm-ups, median of 5 (SURVEY 8d protocol; `--no-cpu-baseline` skips it and the parity records).  `parity` = the
+benchmarked widths and dtype against the fp32 oracle.
 """
 import argparse
 import json
@@ -44,6 +55,29 @@ PEAK_MFMA_TFLOPS = {"bf16": 2500.0, "f32": 157.3}  # dense, MI355X_MICROARCH.md
 # fp32-MFMA peak (157.3) gave fractions above 1
 PEAK_F32_SPLIT_TFLOPS = {1: 2500.0 / 4, 2: 2500.0 / 3}
 PEAK_HBM_GBS = 8000.0
+SETTLE_STEPS = 8  # untimed steps after --warmup: TrainEngine.AUTO_GIVE_UP bounds the auto graph-mode decision by this many
+DUMP_SAMPLE = 1 << 16  # elements kept of a larger state tensor by --dump-outputs
+DUMP_BUDGET = 64 << 20  # bytes written by --dump-outputs at most
+
+
+def dump_outputs(path, loss, model):
+    """`loss` and `model.state_dict()` of the last timed step as DIR/<name>.npy in float32 (see the module docstring).  Sample
+    indices come from a CPU generator seeded by the tensor's position in the state dict: identical for identical arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    state = [(k, v) for k, v in model.state_dict().items() if v.is_floating_point()]
+    cap = min(DUMP_SAMPLE, (DUMP_BUDGET - 4096) // (4 * max(1, len(state))))
+    arrays = {"loss": loss.detach().float().cpu().numpy()}
+    for i, (k, v) in enumerate(state):
+        flat = v.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = torch.randint(flat.numel(), (cap,), generator=torch.Generator().manual_seed(9001 + i))
+            flat = flat[idx.to(flat.device)]
+        arrays["state." + k] = flat.float().cpu().numpy().reshape(v.shape if flat.numel() == v.numel() else (-1,))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
 
 
 def synth_batch(b, s, seed, k1=3):
@@ -257,7 +291,12 @@ def main():
                          "intensity pipeline (al_trainer.py:670-697 + RandomElastic) -> JointResize -> train step, all timed")
     ap.add_argument("--dropout", type=float, default=0.1,
                     help="Dropout2d probability of every PlainBlock (al_train default 0.1, al_trainer.py:109); 0 = None")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / per-kernel records, host-fed and "
+                         "augmentation-free step times, CPU baseline, parity records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and model state of the last timed step as DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity records")
     ap.add_argument("--graph", action="store_true",
                     help="replay the train step from a captured hipGraph (TrainEngine(graph=True); single GPU; for the launch-bound small "
                          "configs: the per-launch roofline probes cannot see into a replay, so `roofline` is omitted)")
@@ -396,8 +435,9 @@ def main():
             nbytes = (2.0 * (pieces + 1) + 1.0) * val(cargs[10]) * val(cargs[11]) * val(cargs[12]) * es
         stream_log[key].append((e0, e1, nbytes))
 
-    ops.call = timed_call
-    ops.PROBE = probe
+    if args.full:
+        ops.call = timed_call
+        ops.PROBE = probe
 
     def sync():
         torch.cuda.synchronize()
@@ -408,14 +448,14 @@ def main():
     n_warm = max(args.warmup, TrainEngine.GRAPH_WARMUP + 1) if args.graph else args.warmup  # graph mode: past the capture
     for i in range(n_warm):
         loss = one_step()
-    # the engine's auto graph mode decides (and captures) within its first steps: let it settle before the timed region
-    extra = 0
-    while extra < 8 and ((eng.graph_mode and not eng._graphs) or (eng.graph_auto and not eng.graph_mode)):
+    # the engine's auto graph mode decides (and captures) within its first steps: let it settle before the timed region.  Always
+    # SETTLE_STEPS of them, however soon it decides, so the state the timed steps start from does not depend on timing.
+    for _ in range(SETTLE_STEPS):
         loss = one_step()
-        extra += 1
     sync()
     replaying = bool(eng.graph_mode)  # --graph, or the engine's auto mode found the warm-up steps host-bound
-    probes = not replaying and os.environ.get("MIA_BENCH_PROBES", "1") != "0"  # (0: A/B of what the instrumentation itself costs)
+    # (MIA_BENCH_PROBES=0: A/B of what the instrumentation itself costs)
+    probes = args.full and not replaying and os.environ.get("MIA_BENCH_PROBES", "1") != "0"
     probe.enabled = probes
     stream_on[0] = probes
     t0 = time.perf_counter()
@@ -423,7 +463,9 @@ def main():
         loss = one_step()
     sync()
     elapsed = time.perf_counter() - t0
-    if not replaying:  # two extra steps, outside the timed region, with every conv / stream launch bracketed (roofline sub-records)
+    if args.dump_outputs and rank == 0:  # before anything below trains the model further
+        dump_outputs(args.dump_outputs, loss, model)
+    if args.full and not replaying:  # two extra steps, outside the timed region, with every conv / stream launch bracketed (roofline sub-records)
         sweep_on[0] = True
         sweep_from[0] = len(probe.pairs)
         for v in stream_log.values():
@@ -435,7 +477,7 @@ def main():
     probe.enabled = False
     stream_on[0] = False
     elapsed_noaug = None
-    if aug is not None:  # the same step on a fixed, already augmented batch: what the pipeline costs (reported, not `value`)
+    if args.full and aug is not None:  # the same step on a fixed, already augmented batch: what the pipeline costs (reported, not `value`)
         fixed = aug(*aug_in)
         for _ in range(2):
             eng.train_step(fixed)
@@ -449,7 +491,7 @@ def main():
     # output, al_trainer.py:1366-1368): pageable CPU tensors in, staged by training.feed.HostFeed (pinned ring, side-stream H2D, labels
     # as bytes), everything inside the timed region.  Reported beside `value`, never as `value` (inputs resident in HBM).
     elapsed_host = host_bytes = None
-    if world == 1:
+    if args.full and world == 1:
         if aug is None:
             host_batch = {"image": img.clone(), "label": lab.clone()}
             host_step = lambda: eng.train_step(host_batch)
@@ -604,7 +646,9 @@ def main():
                "config": {"workload": f"UNet-2D channels {channels} {size}x{size} 1ch, batch {batch}/GPU, {args.norm} norm, "
                                       f"dropout {drop}, Dice+CE, Adam(wd 5e-4), clip 10 ({args.config})",
                           "global_batch": world * batch, "parallelism": f"dp{world}"},
-               "final_loss": round(loss_v, 6), "roofline": roof}
+               "final_loss": round(loss_v, 6)}
+        if args.full:
+            out["roofline"] = roof
         if replaying:
             out["config"]["graph"] = ("train step replayed from one captured hipGraph" + ("" if args.graph else " (TrainEngine auto mode: the warm-up steps were host-bound)")
                                       + "; per-launch roofline probes cannot see into a replay")
@@ -623,7 +667,7 @@ def main():
             out["value_without_augmentation"] = round(world * batch * args.steps / elapsed_noaug, 2)
             out["ms_per_step_without_augmentation"] = round(1e3 * elapsed_noaug / args.steps, 3)
             out["config"]["workload"] += "; inputs: native-resolution batch resident in HBM -> on-GPU elastic+affine+intensity pipeline -> resize, inside the timed step"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(channels, size)
             out["parity"] = parity_gate_benchmarked(dev, channels, dt)
             out["parity_cfg1"] = parity_gate(dev)

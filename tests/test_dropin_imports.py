@@ -2,7 +2,8 @@
 modules only the reference has still come from the reference, and the hot-path modules come from this repo
 (reference import sites: src/entry/activelearning/train.py:3, src/training/al_trainer.py:31-84).
 
-Dev-container test: skipped where /root/reference does not exist (the GPU box)."""
+The reference's `src/` is a stand-in built under a temporary directory: the package and module paths these tests reach
+(REF_LAYOUT), each file a one-line placeholder that defines the names `al_trainer.py`'s import lines take from it."""
 import json
 import os
 import subprocess
@@ -12,9 +13,52 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "medical-image-analysis_amd")
-REF_SRC = "/root/reference/src"
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="reference tree not present")
+# src/ of the reference as far as the tests below reach into it: modules only the reference has, modules this repo also
+# defines (the repo's must win, except under `transforms`), and the marker `training/al_trainer.py` (mia_hip/dropin.py)
+REF_LAYOUT = {
+    "training/__init__.py": "",
+    "training/al_trainer.py": "",
+    "training/base_trainer.py": "class BaseTrainer:\n    pass\n",
+    "training/engine.py": "",
+    "models/__init__.py": "",
+    "models/_unet.py": "class _UNet:\n    pass\n",
+    "models/unet/__init__.py": "",
+    "models/unet/blocks.py": "",
+    "models/unet/unet.py": "",
+    "models/unet/unet_processor.py": "",
+    "metric/__init__.py": "from .metric import cal_hd\n",
+    "metric/metric.py": "def cal_hd(a_np, b_np, spacing=None):\n    raise NotImplementedError\n",
+    "scheduler/__init__.py": "",
+    "scheduler/lr_scheduler.py": "",
+    "scheduler/ramps.py": "class BaseRampUp:\n    pass\n",
+    "losses/__init__.py": "",
+    "losses/adv_loss.py": "",
+    "losses/ce_loss.py": "",
+    "losses/compound_losses.py": "",
+    "losses/dice_loss.py": "",
+    "activelearning/__init__.py": "",
+    "activelearning/active_selector.py": "",
+    "activelearning/badge_selector.py": "",
+    "transforms/__init__.py": "",
+    "transforms/common.py": "",
+    "transforms/image_transform.py": "",
+    "transforms/joint_transform.py": "",
+    "transforms/normalization.py": "",
+    "datasets/__init__.py": "",
+    "utils/__init__.py": "",
+}
+
+
+@pytest.fixture(scope="module")
+def ref_src(tmp_path_factory):
+    src = tmp_path_factory.mktemp("reference") / "src"
+    for rel, text in REF_LAYOUT.items():
+        f = src / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text)
+    return str(src)
+
 
 PROBE = r"""
 import importlib.util, json, sys
@@ -36,36 +80,36 @@ def _resolve(names, pythonpath):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def test_reference_only_modules_resolve_into_the_reference():
+def test_reference_only_modules_resolve_into_the_reference(ref_src):
     names = ["training.al_trainer", "training.base_trainer", "models._unet", "metric.metric", "scheduler.ramps",
              "losses.adv_loss", "activelearning.badge_selector", "datasets", "utils"]  # last two: top-level, not executed
-    got = _resolve(names, [PKG, REF_SRC])
+    got = _resolve(names, [PKG, ref_src])
     for n in names:
-        assert isinstance(got[n], str) and got[n].startswith(REF_SRC + os.sep), (n, got[n])
+        assert isinstance(got[n], str) and got[n].startswith(ref_src + os.sep), (n, got[n])
 
 
-def test_hot_path_modules_resolve_into_this_repo():
+def test_hot_path_modules_resolve_into_this_repo(ref_src):
     names = ["models.unet", "models.unet.unet", "models.unet.blocks", "losses.dice_loss", "losses.compound_losses",
              "losses.ce_loss", "scheduler.lr_scheduler", "training.engine", "metric.segmentation", "activelearning.selectors",
              "transforms.hip.joint_transform", "transforms.hip.image_transform", "transforms.gpu_pipeline", "mia_hip"]
-    got = _resolve(names, [PKG, REF_SRC])
+    got = _resolve(names, [PKG, ref_src])
     for n in names:
         assert isinstance(got[n], str) and got[n].startswith(PKG + os.sep), (n, got[n])
 
 
-def test_dataloader_workers_get_the_reference_cpu_transforms():
+def test_dataloader_workers_get_the_reference_cpu_transforms(ref_src):
     """Per-sample transforms run on CPU tensors in forked DataLoader workers (fugc_dataset.py:140-164): with the
     reference on the path they must be the reference's classes, never the device-only HIP ones."""
     names = ["transforms.common", "transforms.image_transform", "transforms.joint_transform", "transforms.normalization"]
-    got = _resolve(names, [PKG, REF_SRC])
+    got = _resolve(names, [PKG, ref_src])
     for n in names:
-        assert isinstance(got[n], str) and got[n].startswith(REF_SRC + os.sep), (n, got[n])
+        assert isinstance(got[n], str) and got[n].startswith(ref_src + os.sep), (n, got[n])
     alone = _resolve(names, [PKG])  # stand-alone: the same names are the HIP classes
     for n in names:
         assert isinstance(alone[n], str) and alone[n].startswith(PKG + os.sep), (n, alone[n])
 
 
-def test_al_trainer_import_lines_execute():
+def test_al_trainer_import_lines_execute(ref_src):
     """Execute the al_trainer.py:31-84 imports that need nothing absent from this image (torchvision / wandb / medpy /
     SimpleITK are not installed here, so `training.al_trainer` itself cannot be executed -- SURVEY 8c)."""
     code = r"""
@@ -85,15 +129,15 @@ assert all(hasattr(al, n) for n in names)
 import models.unet.unet as u, losses.dice_loss as d, training.base_trainer as b, models._unet as r
 print(u.__file__); print(d.__file__); print(b.__file__); print(r.__file__)
 """
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([PKG, REF_SRC]))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([PKG, ref_src]))
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd="/tmp")
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().splitlines()[-4:]
     assert lines[0].startswith(PKG) and lines[1].startswith(PKG)
-    assert lines[2].startswith(REF_SRC) and lines[3].startswith(REF_SRC)
+    assert lines[2].startswith(ref_src) and lines[3].startswith(ref_src)
 
 
-def test_decoy_packages_on_the_path_are_not_merged(tmp_path):
+def test_decoy_packages_on_the_path_are_not_merged(tmp_path, ref_src):
     """A foreign `transforms` / `models` package on sys.path (site-packages, a working directory) must not be merged into the
     drop-in: only the reference's src/ (marker training/al_trainer.py, or MIA_REFERENCE_SRC) is."""
     decoy = tmp_path / "decoy"
@@ -105,10 +149,10 @@ def test_decoy_packages_on_the_path_are_not_merged(tmp_path):
     names = ["transforms.common", "models._unet", "training.base_trainer", "training.al_trainer"]
     # decoy in front of the reference on the path (a decoy in the WORKING directory of `python -c` shadows every PYTHONPATH
     # entry by Python's own rules, before any of this repo's code runs -- not something a package can defend against)
-    got = _resolve(names, [PKG, str(decoy), REF_SRC])
-    assert got["transforms.common"].startswith(REF_SRC + os.sep), got
-    assert got["models._unet"].startswith(REF_SRC + os.sep), got
-    assert got["training.base_trainer"].startswith(REF_SRC + os.sep), got
+    got = _resolve(names, [PKG, str(decoy), ref_src])
+    assert got["transforms.common"].startswith(ref_src + os.sep), got
+    assert got["models._unet"].startswith(ref_src + os.sep), got
+    assert got["training.base_trainer"].startswith(ref_src + os.sep), got
     # without the reference, the decoy is still ignored: this repo's alias module serves transforms.common, the others are absent
     got = _resolve(["transforms.common", "models._unet"], [PKG, str(decoy)])
     assert got["transforms.common"].startswith(PKG + os.sep), got

@@ -1,6 +1,7 @@
 cd /root/repo
+OUT=${OUT:-out}; mkdir -p "$OUT"
 run() { # cfg steps extra-env graphflag
-  out=$(env $3 python bench.py --config $1 --steps $2 --warmup 5 --no-cpu-baseline $4 2>gpurun_out/r4g_err.txt | tail -1)
+  out=$(env $3 python bench.py --full --config $1 --steps $2 --warmup 5 --no-cpu-baseline $4 2>$OUT/r4g_err.txt | tail -1)
   python - "$1" "$3" "$4" <<PY
 import json,sys
 d=json.loads('''$out''')
