@@ -427,6 +427,15 @@ int mia_argmax_dice(const float* logits, const long long* labels, long long* pre
 int mia_selector_scores_workspace(int nb, int slabs); /* floats */
 int mia_selector_scores(const float* logits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, float smooth, int slabs,
                         float* workspace, float* scores, void* stream);
+/* HD (ITK HausdorffDistanceImageFilter) and ASD (medpy asd, connectivity 1) of calculate_metric_percase
+ * (al_trainer.py:1539-1556) for k1 mask pairs per volume: mask 0 = (pred > 0, labels > 0), mask c = (pred == c, labels == c).
+ * ndim 2: d == 1, 4-neighbour borders, sd unused; ndim 3: 6-neighbour borders.  hd / asd [nvol][k1];
+ * NaN where the prediction mask is empty, +inf where only the label mask is.  pred / labels int64 [nvol][d][h][w]; spacing
+ * (sd, sh, sw) in array axis order, finite, > 0, with s^2 a normal fp32.  Limits: d <= 1024, h, w <= 4096, nvol * k1 <= 209715.
+ * Workspace: 3 floats + 1 byte per voxel + <= 2^20 floats of partials, whatever k1 (masks run one at a time). */
+int mia_surface_distance_workspace(int nvol, int d, int h, int w, int k1); /* floats; < 0 if it does not fit an int */
+int mia_surface_distance(const long long* pred, const long long* labels, int nvol, int ndim, int d, int h, int w, int k1,
+                         float sd, float sh, float sw, float* workspace, float* hd, float* asd, void* stream);
 
 #ifdef __cplusplus
 }
