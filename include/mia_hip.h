@@ -437,6 +437,25 @@ int mia_surface_distance_workspace(int nvol, int d, int h, int w, int k1); /* fl
 int mia_surface_distance(const long long* pred, const long long* labels, int nvol, int ndim, int d, int h, int w, int k1,
                          float sd, float sh, float sw, float* workspace, float* hd, float* asd, void* stream);
 
+/* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
+/* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per
+ * model: prob_sum[nb][k1][hw] (planar fp32) = (first ? 0 : prob_sum) + weight * softmax_k(logits); pred != NULL also receives the
+ * arg-max over classes of the updated sum as int64 [nb][hw], ties to the lowest class (torch.argmax).  prob_sum may be NULL only
+ * with `first` set and pred given (one model: the plain arg-max).  Logits are addressed by (sn, sk, sp) element strides like
+ * mia_argmax_dice; 1 <= k1 <= 8.  One thread owns a pixel, models accumulate in call order, no atomics: bit-identical run to run.
+ * Four pixels per thread with 16-byte accesses for planar (sp == 1) and channels-last (sk == 1, sp == k1) logits when hw % 4 == 0
+ * and the pointers / strides are 16-byte aligned; one pixel per thread otherwise. */
+int mia_softmax_accum(const float* logits, float* prob_sum, long long* pred, int nb, int64_t hw, int k1, int64_t sn, int64_t sk,
+                      int64_t sp, float weight, int first, void* stream);
+/* UnetProcessor.denoise_masks = denoise_one_mask (predict.py:55-90, models/unet/unet_processor.py:72-160) for nb int64 label maps
+ * [nb][h][w] in one launch.  Each of the binary masks `in > 0` and `in == 1` is zero-padded by max(dilate, erode), dilated, eroded,
+ * eroded and dilated with (2r+1)^2 rectangles clipped to the padded domain, cropped, blurred with the smooth_k-tap 8.8 fixed-point
+ * Gaussian (BORDER_REFLECT_101) and thresholded at 1/2; out = 2, 1 where the cleaned class-1 mask is set, 0 where the cleaned object
+ * mask is empty.  Bit-exact integer arithmetic.  in != out.  Supported: 0 <= dilate, erode <= 8, smooth_k in {1, 3, 5, 7},
+ * smooth_k / 2 < h, w <= 2^20; mia_mask_denoise returns MIA_EUNSUPPORTED where mia_mask_denoise_supported returns 0. */
+int mia_mask_denoise_supported(int h, int w, int dilate, int erode, int smooth_k);
+int mia_mask_denoise(const long long* in, long long* out, int nb, int h, int w, int dilate, int erode, int smooth_k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,10 @@
 (reference `src/models/unet/unet_processor.py:11-70`): bilinear resize in, nearest resize back.
 ``denoise_one_mask`` (reference :72-160, only with ``--postprocess-mask``) is OpenCV morphology on the host in the reference; here
 it is the same sequence of operations as batched tensor ops on the device the masks live on (cv2 is not importable in this image:
-the arithmetic below follows OpenCV's documented behaviour for uint8 0 / 255 masks and is "parity unpinned" against cv2 itself)."""
+the arithmetic below follows OpenCV's documented behaviour for uint8 0 / 255 masks and is "parity unpinned" against cv2 itself).
+int64 label maps on the GPU go through one fused kernel instead (``mia_mask_denoise``, csrc/predict.hip: same bits, one launch);
+the tensor path stays the definition, serves CPU tensors and everything the kernel does not cover, and is what
+``denoise_masks(..., backend="tensor")`` runs."""
 from __future__ import annotations
 
 import torch
@@ -82,12 +85,35 @@ class UnetProcessor:
         x = x[..., pad:x.shape[-2] - pad, pad:x.shape[-1] - pad]
         return _smooth_threshold(x, self.smooth_kernel)
 
-    def denoise_masks(self, masks: torch.Tensor) -> torch.Tensor:
+    def _kernel_covers(self, masks: torch.Tensor) -> bool:
+        """True where `mia_mask_denoise` handles these masks: int64 [B,H,W] on the GPU with sizes the kernel supports."""
+        if not (masks.is_cuda and masks.dtype == torch.int64 and masks.ndim == 3 and masks.numel() > 0):
+            return False
+        from mia_hip import lib
+        return bool(lib().mia_mask_denoise_supported(int(masks.shape[-2]), int(masks.shape[-1]), int(self.dilate_size),
+                                                     int(self.erode_size), int(self.smooth_kernel)))
+
+    def denoise_masks(self, masks: torch.Tensor, backend: str = "auto") -> torch.Tensor:
         """`denoise_one_mask` (reference :72-110) for a batch [B,H,W] of label maps: the object mask (all classes) and the mask of
         class 1 are cleaned separately, then the map is rebuilt as 2 everywhere, 1 where the cleaned class-1 mask is set, 0 where
-        the cleaned object mask is empty (`num_classes = 2` is hard-coded in the reference)."""
+        the cleaned object mask is empty (`num_classes = 2` is hard-coded in the reference).
+        backend: "auto" = the fused kernel where it applies, else the tensor ops; "tensor" = the tensor ops; "kernel" = the fused
+        kernel or an error.  All give the same label map."""
+        if backend not in ("auto", "tensor", "kernel"):
+            raise ValueError(f"backend={backend!r}: expected 'auto', 'tensor' or 'kernel'")
         if masks.ndim == 2:
-            return self.denoise_masks(masks.unsqueeze(0))[0]
+            return self.denoise_masks(masks.unsqueeze(0), backend)[0]
+        if backend != "tensor" and self._kernel_covers(masks):
+            from mia_hip import call
+            from mia_hip.ops import _p, _stream
+            src = masks.contiguous()
+            out = torch.empty_like(src)
+            call("mia_mask_denoise", _p(src), _p(out), src.shape[0], src.shape[1], src.shape[2], int(self.dilate_size),
+                 int(self.erode_size), int(self.smooth_kernel), _stream())
+            return out
+        if backend == "kernel":
+            raise ValueError(f"mia_mask_denoise does not cover {masks.dtype} masks of shape {tuple(masks.shape)} on {masks.device} with "
+                             f"sizes ({self.dilate_size}, {self.erode_size}, {self.smooth_kernel})")
         obj = self._denoise_binary((masks > 0).float().unsqueeze(1)).squeeze(1)
         cls1 = self._denoise_binary((masks == 1).float().unsqueeze(1)).squeeze(1)
         out = torch.full_like(masks, 2)
