@@ -342,6 +342,41 @@ int mia_norm_act_bwd_head_w(const float* dlogits, const float* w, int k1, int64_
                             float* dbias, int accumulate, float* head_workspace, float* dw_head, float* db_head,
                             int accumulate_head, void* amax_out, void* stream);
 
+/* ------------------------------------------------------------------ fold-trainer losses (src/losses: DC_and_CE_loss, TopKLoss) */
+/* Masked soft Dice + (weighted) cross-entropy in one pass, with an ignore label and the hard tp/fp/fn of the arg-max prediction:
+ *   valid = (label != ignore_label), p = softmax(logits) (MIA_SEGLOSS_SOFTMAX) or the logits, t = onehot(label) where valid
+ *   I = sum valid p t, P = sum valid p, G = #{valid, label = k} per (image, class);  CE = sum valid w[label] nll / sum valid w[label]
+ *   dc = -mean_k (2I + smooth) / max(G + P + smooth, 1e-8)  (MemoryEfficientSoftDiceLoss, dice_loss.py:100-165; class 0 dropped without
+ *   MIA_SEGLOSS_DO_BG; I, P, G summed over the batch first with MIA_SEGLOSS_BATCH)
+ * out[0] = ce_w*CE + dice_w*dc, out[1] = CE (0 when no pixel is valid), out[2] = dc; counts [B][K1][3] = int64 (tp, fp, fn);
+ * coef: nb*k1*2 + 1 floats for the backward.  labels: int64 [B][HW], or uint8 with MIA_SEGLOSS_LABEL_U8; class_w: K1 floats or NULL;
+ * ignore_label is read only with MIA_SEGLOSS_IGNORE.  A label that is neither a class nor the ignore label: NaN results and the sticky
+ * verdict in bad_label[1], exactly as mia_dice_ce_fwd.  Results are bit-identical run to run (no float atomics); no host sync. */
+#define MIA_SEGLOSS_SOFTMAX 1
+#define MIA_SEGLOSS_DO_BG 2
+#define MIA_SEGLOSS_BATCH 4
+#define MIA_SEGLOSS_LABEL_U8 8
+#define MIA_SEGLOSS_IGNORE 16
+int mia_seg_loss_workspace(int nb, int k1, int slabs); /* floats; the buffer must be 8-byte aligned */
+int mia_seg_loss_fwd(const float* logits, const void* labels, const float* class_w, int nb, int64_t hw, int k1, int64_t sn,
+                     int64_t sk, int64_t sp, int flags, int64_t ignore_label, float smooth, float dice_w, float ce_w, int slabs,
+                     float* workspace, float* coef, float* out, int64_t* counts, int* bad_label, void* stream);
+int mia_seg_loss_bwd(const float* logits, const void* labels, const float* class_w, const float* coef, const float* grad_out,
+                     float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk,
+                     int64_t gsp, int flags, int64_t ignore_label, void* stream);
+/* TopKLoss (ce_loss.py:18-32): mean of the n_top largest per-pixel losses nll = valid w[label] (logsumexp - logit[label]); ignored
+ * pixels count as 0.  The n_top-th largest value tau is found by a radix select over the bit patterns (integer atomics only), then
+ * out[0] = (sum_{nll > tau} nll + (n_top - #{nll > tau}) tau) / n_top.  Backward: nll > tau -> w[label] (p - t) / n_top; the m pixels
+ * with nll == tau share the remaining n_top - #{nll > tau} slots equally (m = 1 unless values tie exactly).  n_top = 0: NaN.
+ * The workspace of the forward (floats, mia_topk_ce_workspace) is handed to the backward unchanged.  flags: LABEL_U8, IGNORE. */
+int mia_topk_ce_workspace(int64_t n_pixels); /* floats; 0 = too many pixels */
+int mia_topk_ce_fwd(const float* logits, const void* labels, const float* class_w, int nb, int64_t hw, int k1, int64_t sn,
+                    int64_t sk, int64_t sp, int flags, int64_t ignore_label, int64_t n_top, float* workspace, float* out,
+                    int* bad_label, void* stream);
+int mia_topk_ce_bwd(const float* logits, const void* labels, const float* class_w, const float* workspace, const float* grad_out,
+                    float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk,
+                    int64_t gsp, int flags, int64_t ignore_label, void* stream);
+
 /* ------------------------------------------------------------------ optimizer (al_trainer.py:1374-1379) */
 #define MIA_OPT_ADAM 0
 #define MIA_OPT_ADAMW 1

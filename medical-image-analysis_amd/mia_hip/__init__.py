@@ -21,6 +21,7 @@ CONV_G3S1, CONV_G3S2, CONV_G2S2, CONV_T3S2, CONV_T2S2, CONV_G1 = range(6)
 WGRAD_3S1, WGRAD_3S2, WGRAD_2S2 = range(3)
 NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_SOFTMAX, LOSS_DO_BG, LOSS_BATCH, LOSS_SQUARED, LOSS_DENSE = 1, 2, 4, 8, 16
+SEGLOSS_SOFTMAX, SEGLOSS_DO_BG, SEGLOSS_BATCH, SEGLOSS_LABEL_U8, SEGLOSS_IGNORE = 1, 2, 4, 8, 16
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 
 

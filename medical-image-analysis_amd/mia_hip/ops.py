@@ -14,7 +14,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import (BF16, CONV_G1, CONV_G2S2, CONV_G3S1, CONV_G3S2, CONV_T2S2, CONV_T3S2, F32, LOSS_BATCH, LOSS_DO_BG,
-               LOSS_DENSE, LOSS_SOFTMAX, LOSS_SQUARED, NORM_BATCH, NORM_INSTANCE, WGRAD_2S2, WGRAD_3S1, WGRAD_3S2, MiaError, call, lib)
+               LOSS_DENSE, LOSS_SOFTMAX, LOSS_SQUARED, NORM_BATCH, NORM_INSTANCE, SEGLOSS_BATCH, SEGLOSS_DO_BG, SEGLOSS_IGNORE,
+               SEGLOSS_LABEL_U8, SEGLOSS_SOFTMAX, WGRAD_2S2, WGRAD_3S1, WGRAD_3S2, MiaError, call, lib)
 
 LRELU_SLOPE = 0.01
 _c_int, _c_float, _c_i64 = ctypes.c_int, ctypes.c_float, ctypes.c_int64
@@ -1245,6 +1246,142 @@ def check_labels() -> None:
         bad[1].zero_()
         raise MiaError("Dice/CE loss: a label lies outside [0, num_classes] (e.g. 255-valued masks or ignore_index -100); "
                        "the reference raises an index error for such targets")
+
+
+# ------------------------------------------------------------------ fold-trainer losses (masked soft Dice + CE, top-k CE)
+def seg_loss_flags(softmax: bool, do_bg: bool, batch: bool) -> int:
+    return (SEGLOSS_SOFTMAX if softmax else 0) | (SEGLOSS_DO_BG if do_bg else 0) | (SEGLOSS_BATCH if batch else 0)
+
+
+def _seg_loss_inputs(logits, labels, class_w, flags: int, ignore_label):
+    """Common argument handling of SegLossFn / TopKCEFn: fp32 logits with collapsible pixel strides, index labels [B,H,W] as
+    uint8 (kept: one byte per pixel) or int64 (anything else is converted), class weights as K1 fp32 values."""
+    _need_dev(logits, labels, class_w)
+    if logits.ndim != 4:
+        raise NotImplementedError("the HIP segmentation losses implement 2-D inputs [B, K, H, W]")
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    st = _pix_strides(logits)
+    if st is None:
+        logits = logits.contiguous()
+        st = _pix_strides(logits)
+    b, k1, h, w = logits.shape
+    if labels.numel() != b * h * w:
+        raise MiaError(f"labels {tuple(labels.shape)} do not index the pixels of logits {tuple(logits.shape)}")
+    labels = labels.reshape(b, h, w)
+    if labels.dtype == torch.uint8:
+        flags |= SEGLOSS_LABEL_U8
+    elif labels.dtype != torch.long:
+        labels = labels.long()
+    labels = labels.contiguous()
+    if class_w is not None:
+        if class_w.numel() != k1:
+            raise MiaError(f"class weights: {class_w.numel()} values for {k1} classes")
+        class_w = class_w.detach().to(device=logits.device, dtype=torch.float32).contiguous()
+    if ignore_label is not None:
+        flags |= SEGLOSS_IGNORE
+    return logits, labels, class_w, st, flags, int(ignore_label) if ignore_label is not None else 0
+
+
+class SegLossFn(torch.autograd.Function):
+    """ce_w * CrossEntropy(weight, ignore) + dice_w * MemoryEfficientSoftDice(loss_mask = label != ignore) in one pass over the
+    logits (src/losses/compound_losses.py:129-196, dice_loss.py:100-165), plus the hard tp / fp / fn of the arg-max prediction
+    (dice_loss.py:168-225 as the fold trainers call it).  `which` picks the returned scalar: 0 total, 1 ce, 2 dc; the other two
+    and the counts of the latest forward stay readable as `SegLossFn.last_out` ([3] fp32) and `SegLossFn.last_counts`
+    ([B,K1,3] int64)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_w, flags: int, ignore_label, smooth: float, dice_w: float, ce_w: float, which: int):
+        logits, labels, class_w, st, flags, ign = _seg_loss_inputs(logits, labels, class_w, flags, ignore_label)
+        b, k1, h, w = logits.shape
+        hw = h * w
+        slabs = max(1, min(256, hw // 8192))
+        dev = logits.device
+        ws = torch.empty((lib().mia_seg_loss_workspace(b, k1, slabs) + 1) // 2, device=dev, dtype=torch.float64)  # 8-byte aligned
+        coef = torch.empty(b * k1 * 2 + 1, device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
+        out = torch.empty(3, device=dev, dtype=torch.float32)
+        counts = torch.empty((b, k1, 3), device=dev, dtype=torch.int64)
+        bad = _bad_flags(dev)
+        call("mia_seg_loss_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(hw), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]),
+             flags, _c_i64(ign), _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(coef), _p(out), _p(counts),
+             _p(bad), _stream())
+        ctx.save_for_backward(logits, labels, coef)
+        ctx.class_w = class_w
+        ctx.flags, ctx.ign, ctx.st = flags, ign, st
+        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
+        SegLossFn.last_out = out
+        SegLossFn.last_counts = counts
+        return out[which]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, coef = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl = torch.empty_like(logits)  # preserves (dense) strides
+        gst = _pix_strides(dl)
+        g = gout.reshape(1).float().contiguous()
+        st = ctx.st
+        call("mia_seg_loss_bwd", _p(logits), _p(labels), _p(ctx.class_w), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1,
+             _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_i64(ctx.ign),
+             _stream())
+        return dl, None, None, None, None, None, None, None, None
+
+
+SegLossFn.last_out = None
+SegLossFn.last_counts = None
+
+
+class TopKCEFn(torch.autograd.Function):
+    """Mean of the hardest k % of the per-pixel (weighted, ignore-aware) cross-entropy (src/losses/ce_loss.py:18-32) without a
+    sort: a radix select on the device finds the threshold.  Pixels that tie exactly with the threshold share the remaining
+    slots equally -- this project's own deterministic rule where torch.topk's choice is unspecified."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_w, ignore_label, k: float):
+        logits, labels, class_w, st, flags, ign = _seg_loss_inputs(logits, labels, class_w, 0, ignore_label)
+        b, k1, h, w = logits.shape
+        n_pix = b * h * w
+        n_top = int(n_pix * k / 100)
+        if not 0 <= n_top <= n_pix:
+            raise MiaError(f"TopKLoss: k={k} % selects {n_top} of {n_pix} pixels")
+        dev = logits.device
+        words = lib().mia_topk_ce_workspace(_c_i64(n_pix))
+        if words <= 0:
+            raise MiaError(f"TopKLoss: {n_pix} pixels are more than the radix select indexes")
+        ws = torch.empty(words, device=dev, dtype=torch.float32)
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        bad = _bad_flags(dev)
+        call("mia_topk_ce_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(h * w), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]),
+             flags, _c_i64(ign), _c_i64(n_top), _p(ws), _p(out), _p(bad), _stream())
+        ctx.save_for_backward(logits, labels, ws)
+        ctx.class_w = class_w
+        ctx.flags, ctx.ign, ctx.st = flags, ign, st
+        DiceCEFn.last_bad_label = bad
+        TopKCEFn.last_threshold = ws[n_pix]
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, labels, ws = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl = torch.empty_like(logits)
+        gst = _pix_strides(dl)
+        g = gout.reshape(1).float().contiguous()
+        st = ctx.st
+        call("mia_topk_ce_bwd", _p(logits), _p(labels), _p(ctx.class_w), _p(ws), _p(g), _p(dl), b, _c_i64(h * w), k1, _c_i64(st[0]),
+             _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_i64(ctx.ign), _stream())
+        return dl, None, None, None, None
+
+
+TopKCEFn.last_threshold = None
+
+
+def hard_tp_fp_fn(logits: torch.Tensor, target: torch.Tensor, ignore_label=None) -> torch.Tensor:
+    """int64 [B, K1, 3] = (tp, fp, fn) of the arg-max prediction per image and class, pixels labelled `ignore_label` left out
+    (get_tp_fp_fn_tn(onehot(argmax), target, mask) of the fold trainers' online Dice) -- one kernel pass, no one-hot tensors."""
+    with torch.no_grad():
+        SegLossFn.apply(logits.detach(), target, None, 0, ignore_label, 1.0, 1.0, 1.0, 0)
+    return SegLossFn.last_counts
 
 
 # ------------------------------------------------------------------ optimizer helpers
