@@ -462,6 +462,18 @@ int mia_argmax_dice(const float* logits, const long long* labels, long long* pre
 int mia_selector_scores_workspace(int nb, int slabs); /* floats */
 int mia_selector_scores(const float* logits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, float smooth, int slabs,
                         float* workspace, float* scores, void* stream);
+/* BADGE gradient embeddings of a batch (badge_selector.py:19-35 `image_wise_grad` and :80-96, the loss it differentiates, which
+ * the reference evaluates one image at a time through autograd): embed[nb][k1 * c0] = d(CE(logits, a) + DiceLoss(logits, a)) /
+ * d(weight of the 1x1 head) per image, a = the image's own arg-max labels (ties to the lowest class), entry c * c0 + k like
+ * decoder.seg_output.weight flattened; loss[nb] = that loss per image.  logits fp32 addressed by (sn, sk, sp) element strides like
+ * mia_selector_scores; feat = the head's input, NHWC [nb][hw][c0], dtype MIA_F32 (16-byte aligned) or MIA_BF16 (8-byte aligned);
+ * smooth / do_bg / squared = DiceLoss's (softmax=True; `batch` makes no difference at one image per loss).  1 <= k1 <= 8
+ * (k1 >= 2 unless do_bg), c0 a multiple of 4 up to 128, hw < 2^31.  No atomics, fixed summation order: bit-identical run to run,
+ * and an image's result does not depend on nb or on its position.  The workspace query also returns the number of pixel slabs per
+ * image (a function of hw alone; slabs may be NULL); it returns 0 for an unsupported shape. */
+int mia_badge_embed_workspace(int nb, int64_t hw, int k1, int c0, int dtype, int* slabs); /* floats */
+int mia_badge_embed(const float* logits, const void* feat, int dtype, int nb, int64_t hw, int k1, int c0, int64_t sn, int64_t sk,
+                    int64_t sp, float smooth, int do_bg, int squared, float* workspace, float* embed, float* loss, void* stream);
 /* HD (ITK HausdorffDistanceImageFilter) and ASD (medpy asd, connectivity 1) of calculate_metric_percase
  * (al_trainer.py:1539-1556) for k1 mask pairs per volume: mask 0 = (pred > 0, labels > 0), mask c = (pred == c, labels == c).
  * ndim 2: d == 1, 4-neighbour borders, sd unused; ndim 3: 6-neighbour borders.  hd / asd [nvol][k1];

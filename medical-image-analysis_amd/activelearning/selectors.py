@@ -3,8 +3,10 @@
 
 Same class names, constructor arguments and ``select_next_batch(active_dataset, select_num, model, device)`` contract.
 The per-image arithmetic runs in HIP kernels (``selector_scores``: fused softmax + entropy / confidence / margin
-reduction; ``model.get_enc_feature``: NHWC global average pool); clustering / distance matrices stay on the host with
-scikit-learn exactly as in the reference (kmean_selector.py:143-145,190-192, coreset_selector.py:122-167).
+reduction; ``model.get_enc_feature``: NHWC global average pool; ``badge_embeddings``: the BADGE gradient embeddings of a
+batch from logits and the head's input, opt-in through ``BADGESelector(embed_batch_size=...)``); clustering / distance
+matrices stay on the host with scikit-learn exactly as in the reference (kmean_selector.py:143-145,190-192,
+coreset_selector.py:122-167).
 
 ``active_dataset`` is duck-typed like the reference uses it: ``get_size() -> (labeled, pool)``, ``get_pool_dataset()``,
 ``get_train_dataset()``, ``pool_dataset.image_idx``; datasets yield dicts with ``"image"`` and ``"case_name"``.
@@ -12,6 +14,7 @@ Features loaded from ``feature_path`` (*.h5, kmean_selector.py:77-86) need h5py,
 """
 from __future__ import annotations
 
+import os
 from abc import ABC, abstractmethod
 from pathlib import Path
 from typing import Any, Callable, Optional
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 from torch.utils.data import ConcatDataset, DataLoader
 
-from .scores import CONFIDENCE, ENTROPY, MARGIN, selector_scores
+from .scores import CONFIDENCE, ENTROPY, MARGIN, badge_embeddings, badge_shape_supported, selector_scores
 
 
 class ActiveSelector(ABC):
@@ -260,16 +263,92 @@ def image_wise_grad(loss: torch.Tensor, model, last_layer_name: str = "decoder.s
     return g.detach().flatten().clone()
 
 
+def badge_closed_form_reason(dice_loss, ce_loss, multiple_loss: str, model,
+                             last_layer_name: str = "decoder.seg_output.weight") -> Optional[str]:
+    """None when the batched closed form (``scores.badge_embeddings``) computes exactly what ``BADGESelector`` differentiates,
+    else the reason it does not.  Pure Python, no GPU: the loss must be ``CrossEntropyLoss() + DiceLoss(softmax=True)`` on the
+    arg-max labels, and the model must expose the head's input (``get_pixel_feature``) with a head the kernel supports."""
+    from losses.dice_loss import DiceLoss
+    if multiple_loss != "add":
+        return f"multiple_loss={multiple_loss!r} is not 'add'"
+    if type(ce_loss) is not torch.nn.CrossEntropyLoss:
+        return f"ce_loss is {type(ce_loss).__name__}, not a plain torch.nn.CrossEntropyLoss"
+    if ce_loss.weight is not None:
+        return "ce_loss has class weights"
+    if getattr(ce_loss, "label_smoothing", 0.0) != 0:
+        return "ce_loss has label_smoothing > 0"
+    if ce_loss.reduction != "mean":
+        return f"ce_loss.reduction={ce_loss.reduction!r} is not 'mean'"
+    if not isinstance(dice_loss, DiceLoss):
+        return f"dice_loss is {type(dice_loss).__name__}, not losses.dice_loss.DiceLoss"
+    if not dice_loss.softmax:
+        return "dice_loss has softmax=False"
+    if not callable(getattr(model, "get_pixel_feature", None)):
+        return "the model has no get_pixel_feature"
+    named = getattr(model, "named_parameters", None)
+    last = dict(named()).get(last_layer_name) if callable(named) else None
+    if last is None or last.ndim != 4 or tuple(last.shape[2:]) != (1, 1):
+        return f"the model has no 1x1 head weight {last_layer_name}"
+    k1, c0 = int(last.shape[0]), int(last.shape[1])
+    if not badge_shape_supported(k1, c0):
+        return f"head of {k1} classes over {c0} channels is outside the kernel's range"
+    if k1 != dice_loss.num_classes:
+        return f"dice_loss counts {dice_loss.num_classes} classes, the head has {k1}"
+    if k1 < 2 and not dice_loss.do_bg:
+        return "one class without do_bg leaves the Dice term no class"
+    if 0 <= ce_loss.ignore_index < k1:
+        return f"ce_loss ignores class {ce_loss.ignore_index}"
+    return None
+
+
 class BADGESelector(ActiveSelector):
-    """k-means++ over last-layer gradient embeddings of the pseudo-labelled loss (badge_selector.py:38-128)."""
+    """k-means++ over last-layer gradient embeddings of the pseudo-labelled loss (badge_selector.py:38-128).
+
+    Build-side addition: ``embed_batch_size`` (or, when it is None, the environment variable ``MIA_BADGE_BATCH``).  When set and
+    the configuration is the closed form's (``badge_closed_form_reason``), the pool runs through ``model.get_pixel_feature`` in
+    batches of that size under ``no_grad`` and one fused HIP pass per batch (``scores.badge_embeddings``) returns all its
+    embeddings; otherwise -- and always when neither is set -- the reference's shape runs: one eval-mode forward, loss and
+    autograd gradient per loader batch."""
 
     def __init__(self, dice_loss: Callable, ce_loss: Callable, batch_size: int, num_workers: int, pin_memory: bool = True,
-                 smooth: float = 1e-8, multiple_loss: str = "add") -> None:
+                 smooth: float = 1e-8, multiple_loss: str = "add", embed_batch_size: Optional[int] = None) -> None:
         self.dice_loss, self.ce_loss = dice_loss, ce_loss
         self.batch_size, self.num_workers, self.pin_memory = batch_size, num_workers, pin_memory
         self.multiple_loss, self.smooth = multiple_loss, smooth
+        self.embed_batch_size = embed_batch_size
+
+    def resolved_embed_batch_size(self) -> Optional[int]:
+        """The explicit ``embed_batch_size`` if given, else ``MIA_BADGE_BATCH``, else None (= the fused path is off)."""
+        v = self.embed_batch_size
+        if v is None:
+            env = os.environ.get("MIA_BADGE_BATCH", "").strip()
+            v = int(env) if env else None
+        return int(v) if v is not None and int(v) > 0 else None
+
+    def embed_path(self, model) -> str:
+        """"fused" or "autograd": which path ``cal_scores`` will take for this model (``embed_path_reason`` says why)."""
+        if self.resolved_embed_batch_size() is None:
+            self.embed_path_reason = "no embed_batch_size and no MIA_BADGE_BATCH"
+            return "autograd"
+        self.embed_path_reason = badge_closed_form_reason(self.dice_loss, self.ce_loss, self.multiple_loss, model)
+        return "autograd" if self.embed_path_reason else "fused"
+
+    def _cal_scores_fused(self, active_dataset, model, device, embed_batch_size: int):
+        model.eval()
+        embeds, names = [], []
+        with torch.no_grad():
+            for batch in _loader(active_dataset.get_pool_dataset(), embed_batch_size, self.num_workers, self.pin_memory):
+                names.extend(batch["case_name"])
+                seg, feat = model.get_pixel_feature(batch["image"].to(device))
+                embed, _ = badge_embeddings(seg, feat.permute(0, 2, 3, 1), float(self.dice_loss.smooth), self.dice_loss.do_bg,
+                                            self.dice_loss.squared)
+                embeds.append(embed)
+        model.zero_grad()  # the state the per-image path leaves behind
+        return np.array(names), torch.cat(embeds, dim=0).cpu().numpy()
 
     def cal_scores(self, active_dataset, model, device):
+        if self.embed_path(model) == "fused":
+            return self._cal_scores_fused(active_dataset, model, device, self.resolved_embed_batch_size())
         model.eval()
         embeds, names = [], []
         for batch in _loader(active_dataset.get_pool_dataset(), self.batch_size, self.num_workers, self.pin_memory):
