@@ -15,13 +15,12 @@
 template <typename T>
 __global__ void head_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                 float* __restrict__ out, int64_t npix, int c0, int k1, int64_t osp, int64_t osk,
-                                int64_t osn, int64_t hw) {
+                                int64_t osn, int64_t hw, bool vec) {  // vec: c0 % EPU == 0 and x 16-byte aligned (the host decides)
   extern __shared__ float wsh[];  // [k1][c0]
   for (int i = threadIdx.x; i < k1 * c0; i += blockDim.x) wsh[i] = w[i];
   __syncthreads();
   constexpr int EPU = Elem<T>::EPU;
   const int sub = threadIdx.x & 7;
-  const bool vec = (c0 % EPU) == 0;
   for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3; p < npix; p += ((int64_t)gridDim.x * blockDim.x) >> 3) {
     float acc[MAXK];
 #pragma unroll
@@ -427,10 +426,12 @@ extern "C" int mia_head_fwd(const void* x, int dtype, const float* w, const floa
     MIA_LAUNCH_CHECK();
     return MIA_OK;
   }
+  // 16-byte loads need an aligned x as well as whole units: a view into a larger buffer takes the scalar branch (as in mia_head_bwd)
+  const bool vec = c0 % (dtype == MIA_BF16 ? 8 : 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   if (dtype == MIA_BF16)
-    hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), k1 * c0 * 4, st, static_cast<const bf16_t*>(x), w, b, logits, npix, c0, k1, osp, osk, osn, hw);
+    hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), k1 * c0 * 4, st, static_cast<const bf16_t*>(x), w, b, logits, npix, c0, k1, osp, osk, osn, hw, vec);
   else if (dtype == MIA_F32)
-    hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(blocks), dim3(256), k1 * c0 * 4, st, static_cast<const float*>(x), w, b, logits, npix, c0, k1, osp, osk, osn, hw);
+    hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(blocks), dim3(256), k1 * c0 * 4, st, static_cast<const float*>(x), w, b, logits, npix, c0, k1, osp, osk, osn, hw, vec);
   else { mia_set_error("mia_head_fwd: bad dtype"); return MIA_EARG; }
   MIA_LAUNCH_CHECK();
   return MIA_OK;
@@ -879,7 +880,8 @@ __global__ __launch_bounds__(256) void dice_ce_bwd_fast_kernel(const float* __re
       for (int k = 0; k < K1; ++k) {
         const float t = (lo[j] == (unsigned)k) ? 1.f : 0.f;
         const float dd = (flags & LF_SOFTMAX) ? pr[k] * (gk[k] - dot) : gk[k];
-        o[(j * K1 + k) >> 2][(j * K1 + k) & 3] = ok ? dd + cew * (pr[k] - t) : 0.f;  // dropped pixel: same as the forward
+        // a pixel with a bad label is poisoned like every other one (coef is NaN after such a forward), never a quiet zero
+        o[(j * K1 + k) >> 2][(j * K1 + k) & 3] = ok ? dd + cew * (pr[k] - t) : __builtin_nanf("");
       }
     }
 #pragma unroll
