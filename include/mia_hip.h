@@ -494,6 +494,20 @@ int mia_surface_distance(const long long* pred, const long long* labels, int nvo
  * and the pointers / strides are 16-byte aligned; one pixel per thread otherwise. */
 int mia_softmax_accum(const float* logits, float* prob_sum, long long* pred, int nb, int64_t hw, int k1, int64_t sn, int64_t sk,
                       int64_t sp, float weight, int first, void* stream);
+/* Sliding-window prediction: one pass per (model, mirror combination, window).  For 0 <= i < ph, 0 <= j < pw
+ *   canvas[n][k][y0+i][x0+j] += weight * gy[i] * gx[j] * softmax_k(logits[n][:, i', j']),  i' = flip_h ? ph-1-i : i, j' = flip_w ? pw-1-j : j
+ * logits [nb][k1][ph][pw] fp32 addressed by (sn, sk, sp) element strides like mia_softmax_accum (pixel index i' * pw + j'), canvas
+ * contiguous [nb][k1][h][w] fp32, gy[ph] / gx[pw] fp32 device arrays (the importance map is their outer product), 1 <= k1 <= 8.
+ * The window must lie inside the canvas (MIA_EARG otherwise; nothing is clipped); canvas pixels outside it are not touched.  One
+ * thread owns a canvas pixel, no atomics; a pixel's bits do not depend on the branch that computed it (four pixels per thread with
+ * 16-byte accesses when pw, x0 and w are multiples of 4 and pointers / strides are 16-byte aligned, one pixel otherwise). */
+int mia_window_accum(const float* logits, float* canvas, const float* gy, const float* gx, int nb, int k1, int ph, int pw, int h,
+                     int w, int y0, int x0, int64_t sn, int64_t sk, int64_t sp, float weight, int flip_h, int flip_w, void* stream);
+/* One pass over the canvas: pred (int64 [nb][h][w], may be NULL) = arg-max over k of the raw canvas, ties to the lowest class, taken
+ * before any scaling; with normalise != 0, canvas[n][k][y][x] *= (scale * ry[y]) * rx[x] in place (ry[h], rx[w] fp32 device arrays:
+ * the reciprocal of the separable coverage, sum over window starts of gy[y - y0] resp. gx[x - x0]). */
+int mia_window_finalize(float* canvas, long long* pred, const float* ry, const float* rx, int nb, int k1, int h, int w, float scale,
+                        int normalise, void* stream);
 /* UnetProcessor.denoise_masks = denoise_one_mask (predict.py:55-90, models/unet/unet_processor.py:72-160) for nb int64 label maps
  * [nb][h][w] in one launch.  Each of the binary masks `in > 0` and `in == 1` is zero-padded by max(dilate, erode), dilated, eroded,
  * eroded and dilated with (2r+1)^2 rectangles clipped to the padded domain, cropped, blurred with the smooth_k-tap 8.8 fixed-point

@@ -12,6 +12,12 @@
 //   dilate, erode, erode, dilate on the zero-padded domain, crop, reflect -- is a vertical OR / AND over rows followed by a
 //   log-step shift-OR inside the row.  The 8.8 fixed-point Gaussian and its threshold are integer sums over 7 x 7 bits.  The
 //   result depends on 2 bits per pixel: the kernel reads 8 bytes (x ~3 for the halo, mostly from cache) and writes 8 per pixel.
+// * mia_window_accum / mia_window_finalize: tiled prediction with overlap (the `patch_size` / `stride` fields of the reference's
+//   trainer configs, al_trainer.py:112,167,253, which nothing there reads).  One streaming pass per (model, mirror combination,
+//   window) adds importance * weight * softmax into the window's region of a full-size canvas, reading the logits mirrored where the
+//   input was; one pass at the end takes the arg-max of the raw canvas and scales it by the separable 1 / coverage.  A thread owns a
+//   canvas pixel for a whole pass, windows are separate launches in stream order: no atomics, bit-identical from run to run.  Per
+//   window pixel 4*K1 bytes of logits and 4*K1 read + 4*K1 written of canvas, the canvas part normally from the Infinity Cache.
 #include "common.h"
 
 #define PMAXK 8
@@ -146,6 +152,207 @@ extern "C" int mia_softmax_accum(const float* logits, float* prob_sum, long long
 #define SA_CASE(K) case K: launch_softmax_accum<K>(mode, groups, st, logits, prob_sum, pred, hw, sn, sk, sp, weight, first); break;
     SA_CASE(1) SA_CASE(2) SA_CASE(3) SA_CASE(4) SA_CASE(5) SA_CASE(6) SA_CASE(7) SA_CASE(8)
 #undef SA_CASE
+  }
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+// ------------------------------------------------------------------------------------------- sliding-window prediction
+// canvas[n][k][y0 + i][x0 + j] = fma(gy[i] * gx[j], weight * softmax_k(logits[n][:, i', j']), canvas[...]) with (i', j') the
+// pixel mirrored inside the window where flip_h / flip_w say so.  Every branch below evaluates exactly that expression per
+// pixel -- one multiply for the importance, softmax_w, one explicit fma -- so which branch took a pixel cannot show in its bits.
+enum { WA_SCALAR = 0, WA_PLANAR4 = 1, WA_CLAST4 = 2 };
+
+template <int K1, int MODE>
+__global__ void __launch_bounds__(256) window_accum_kernel(const float* __restrict__ logits, float* __restrict__ canvas,
+                                                           const float* __restrict__ gy, const float* __restrict__ gx, int ph, int pw,
+                                                           int h, int w, int y0, int x0, int64_t total, int64_t sn, int64_t sk,
+                                                           int64_t sp, float weight, int flip_h, int flip_w) {
+  constexpr int PX = MODE == WA_SCALAR ? 1 : 4;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one group of PX pixels of one window row
+  if (idx >= total) return;
+  const int gpr = pw / PX;  // groups per window row
+  const int64_t row = idx / gpr, b = row / ph;
+  const int j = (int)(idx - row * gpr) * PX, i = (int)(row - b * ph);
+  const int si = flip_h ? ph - 1 - i : i;
+  const int sj = flip_w ? pw - PX - j : j;                  // first source column of the group (its last canvas pixel when mirrored)
+  const float* src = logits + b * sn;
+  const int64_t p = (int64_t)si * pw + sj;
+  float v[PX][K1];
+  if (MODE == WA_PLANAR4) {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(src + k * sk + p);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u][k] = t[u];
+    }
+  } else if (MODE == WA_CLAST4) {  // four pixels = K1 consecutive 16-byte units
+    float flat[4 * K1];
+#pragma unroll
+    for (int u = 0; u < K1; ++u) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(src + p * K1 + 4 * u);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) flat[4 * u + q] = t[q];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int k = 0; k < K1; ++k) v[u][k] = flat[u * K1 + k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) v[0][k] = src[p * sp + k * sk];
+  }
+#pragma unroll
+  for (int u = 0; u < PX; ++u) softmax_w<K1>(v[u], weight);
+  const float wy = gy[i];
+  float g[PX];  // importance of canvas pixel j + c
+#pragma unroll
+  for (int c = 0; c < PX; ++c) g[c] = wy * gx[j + c];
+  float* acc = canvas + ((b * K1) * h + (y0 + i)) * (int64_t)w + x0 + j;
+  const int64_t plane = (int64_t)h * w;
+  if (PX == 4) {
+    f32x4 t[K1];
+#pragma unroll
+    for (int k = 0; k < K1; ++k) t[k] = *reinterpret_cast<const f32x4*>(acc + k * plane);
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      if (flip_w) {  // canvas pixel c holds source pixel 3 - c
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[k][c] = __builtin_fmaf(g[c], v[3 - c][k], t[k][c]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[k][c] = __builtin_fmaf(g[c], v[c][k], t[k][c]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      store_data_fence();
+      *reinterpret_cast<f32x4*>(acc + k * plane) = t[k];
+      store_data_pad();  // tools/check_store_hazard.py
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) acc[k * plane] = __builtin_fmaf(g[0], v[0][k], acc[k * plane]);
+  }
+}
+
+template <int K1>
+static void launch_window_accum(int mode, int64_t groups, hipStream_t st, const float* logits, float* canvas, const float* gy,
+                                const float* gx, int ph, int pw, int h, int w, int y0, int x0, int64_t sn, int64_t sk, int64_t sp,
+                                float weight, int flip_h, int flip_w) {
+  const dim3 grid((unsigned)ceil_div64(groups, 256)), block(256);
+#define WA_LAUNCH(M) hipLaunchKernelGGL((window_accum_kernel<K1, M>), grid, block, 0, st, logits, canvas, gy, gx, ph, pw, h, w, y0, x0, \
+                                        groups, sn, sk, sp, weight, flip_h, flip_w)
+  if (mode == WA_PLANAR4) WA_LAUNCH(WA_PLANAR4);
+  else if (mode == WA_CLAST4) WA_LAUNCH(WA_CLAST4);
+  else WA_LAUNCH(WA_SCALAR);
+#undef WA_LAUNCH
+}
+
+extern "C" int mia_window_accum(const float* logits, float* canvas, const float* gy, const float* gx, int nb, int k1, int ph, int pw,
+                                int h, int w, int y0, int x0, int64_t sn, int64_t sk, int64_t sp, float weight, int flip_h, int flip_w,
+                                void* stream) {
+  MIA_CHECK_ARG(logits && canvas && gy && gx && nb > 0 && ph > 0 && pw > 0 && h > 0 && w > 0, "mia_window_accum: bad arguments");
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= PMAXK, "mia_window_accum: k1=%d not in [1,%d]", k1, PMAXK);
+  MIA_CHECK_ARG(y0 >= 0 && x0 >= 0 && (int64_t)y0 + ph <= h && (int64_t)x0 + pw <= w,
+                "mia_window_accum: window %dx%d at (%d,%d) does not lie inside the %dx%d canvas", ph, pw, y0, x0, h, w);
+  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0, "mia_window_accum: negative strides");
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  // four pixels per thread: every group is a 16-byte aligned unit of the logits (mirrored or not) and of the canvas
+  const bool quad = pw % 4 == 0 && x0 % 4 == 0 && w % 4 == 0 && al16(logits) && sn % 4 == 0 && al16(canvas);
+  int mode = WA_SCALAR;
+  if (quad && sp == 1 && sk % 4 == 0) mode = WA_PLANAR4;
+  else if (quad && sk == 1 && sp == k1) mode = WA_CLAST4;
+  const int64_t groups = (int64_t)nb * ph * (mode == WA_SCALAR ? pw : pw / 4);
+  MIA_CHECK_ARG(ceil_div64(groups, 256) <= 0x7fffffffLL, "mia_window_accum: nb * ph * pw = %lld is too large", (long long)nb * ph * pw);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k1) {
+#define WA_CASE(K) case K: launch_window_accum<K>(mode, groups, st, logits, canvas, gy, gx, ph, pw, h, w, y0, x0, sn, sk, sp, weight, flip_h != 0, flip_w != 0); break;
+    WA_CASE(1) WA_CASE(2) WA_CASE(3) WA_CASE(4) WA_CASE(5) WA_CASE(6) WA_CASE(7) WA_CASE(8)
+#undef WA_CASE
+  }
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+// pred = arg-max over classes of the raw canvas, then (normalise) canvas *= (scale * ry[y]) * rx[x]; PX pixels of one row per thread
+template <int K1, int PX>
+__global__ void __launch_bounds__(256) window_finalize_kernel(float* __restrict__ canvas, long long* __restrict__ pred,
+                                                              const float* __restrict__ ry, const float* __restrict__ rx, int h, int w,
+                                                              int64_t total, float scale, int normalise) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int gpr = w / PX;
+  const int64_t row = idx / gpr, b = row / h;
+  const int x = (int)(idx - row * gpr) * PX, y = (int)(row - b * h);
+  const int64_t plane = (int64_t)h * w;
+  float* acc = canvas + (b * K1) * plane + (int64_t)y * w + x;
+  float v[PX][K1];
+#pragma unroll
+  for (int k = 0; k < K1; ++k) {
+    if (PX == 4) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(acc + k * plane);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c][k] = t[c];
+    } else {
+      v[0][k] = acc[k * plane];
+    }
+  }
+  if (pred) {
+    long long* dst = pred + b * plane + (int64_t)y * w + x;
+    if (PX == 4) {
+      typedef __attribute__((ext_vector_type(2))) long long i64x2;
+      const i64x2 lo = i64x2{argmax_first<K1>(v[0]), argmax_first<K1>(v[1])}, hi = i64x2{argmax_first<K1>(v[2]), argmax_first<K1>(v[3])};
+      store_data_fence();
+      *reinterpret_cast<i64x2*>(dst) = lo;
+      store_data_pad();  // tools/check_store_hazard.py
+      *reinterpret_cast<i64x2*>(dst + 2) = hi;
+      store_data_pad();
+    } else {
+      dst[0] = argmax_first<K1>(v[0]);
+    }
+  }
+  if (normalise) {
+    const float sy = scale * ry[y];
+    float s[PX];
+#pragma unroll
+    for (int c = 0; c < PX; ++c) s[c] = sy * rx[x + c];
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      if (PX == 4) {
+        f32x4 t;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t[c] = v[c][k] * s[c];
+        store_data_fence();
+        *reinterpret_cast<f32x4*>(acc + k * plane) = t;
+        store_data_pad();
+      } else {
+        acc[k * plane] = v[0][k] * s[0];
+      }
+    }
+  }
+}
+
+extern "C" int mia_window_finalize(float* canvas, long long* pred, const float* ry, const float* rx, int nb, int k1, int h, int w,
+                                   float scale, int normalise, void* stream) {
+  MIA_CHECK_ARG(canvas && nb > 0 && h > 0 && w > 0, "mia_window_finalize: bad arguments");
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= PMAXK, "mia_window_finalize: k1=%d not in [1,%d]", k1, PMAXK);
+  MIA_CHECK_ARG(pred || normalise, "mia_window_finalize: nothing to do without pred and without normalise");
+  MIA_CHECK_ARG(!normalise || (ry && rx), "mia_window_finalize: normalise needs ry and rx");
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const bool quad = w % 4 == 0 && al16(canvas) && (!pred || al16(pred));
+  const int64_t groups = (int64_t)nb * h * (quad ? w / 4 : w);
+  MIA_CHECK_ARG(ceil_div64(groups, 256) <= 0x7fffffffLL, "mia_window_finalize: nb * h * w = %lld is too large", (long long)nb * h * w);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)ceil_div64(groups, 256)), block(256);
+  switch (k1) {
+#define WF_CASE(K)                                                                                                                      \
+  case K:                                                                                                                               \
+    if (quad) hipLaunchKernelGGL((window_finalize_kernel<K, 4>), grid, block, 0, st, canvas, pred, ry, rx, h, w, groups, scale, normalise); \
+    else hipLaunchKernelGGL((window_finalize_kernel<K, 1>), grid, block, 0, st, canvas, pred, ry, rx, h, w, groups, scale, normalise);     \
+    break;
+    WF_CASE(1) WF_CASE(2) WF_CASE(3) WF_CASE(4) WF_CASE(5) WF_CASE(6) WF_CASE(7) WF_CASE(8)
+#undef WF_CASE
   }
   MIA_LAUNCH_CHECK();
   return MIA_OK;

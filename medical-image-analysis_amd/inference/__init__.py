@@ -1,2 +1,4 @@
-"""Prediction with trained models: the fold ensemble of the reference's `entry/fugc2025/predict.py` on the GPU."""
-from .predictor import EnsemblePredictor, ensemble_predict, softmax_accum  # noqa: F401
+"""Prediction with trained models: the fold ensemble of the reference's `entry/fugc2025/predict.py` on the GPU, and tiled
+prediction with Gaussian blending and mirroring at the images' own resolution."""
+from .predictor import (EnsemblePredictor, ensemble_predict, sliding_window_predict, softmax_accum, window_accum,  # noqa: F401
+                        window_finalize, window_starts, window_weights)
