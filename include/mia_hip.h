@@ -376,6 +376,40 @@ int mia_topk_ce_fwd(const float* logits, const void* labels, const float* class_
 int mia_topk_ce_bwd(const float* logits, const void* labels, const float* class_w, const float* workspace, const float* grad_out,
                     float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk,
                     int64_t gsp, int flags, int64_t ignore_label, void* stream);
+/* Region-based loss (compound_losses.py:178-233, DC_and_BCE_loss: sigmoid soft Dice + BCEWithLogitsLoss): one sigmoid output per
+ * region, regions may overlap, multi-label target with an optional ignore channel.  Per valid pixel and channel, p = sigmoid(z):
+ *   I += p t, P += p, G += t;  bce += pos_weight[c] t softplus(-z) + (1 - t) softplus(z)
+ *   dc = -mean (2I + smooth) / max(G + P + smooth, 1e-8)  (channel 0 dropped without MIA_REGLOSS_DO_BG; I, P, G summed over the batch
+ *   first with MIA_REGLOSS_BATCH, else the mean runs over (image, channel))
+ *   CE = bce / (nb c hw) without MIA_REGLOSS_IGNORE; with it bce / max(#valid pixels, 1e-8): the sum runs over the valid pixels and
+ *   ALL c channels, the divisor counts PIXELS (the reference's mask broadcasts over the channels)
+ * out[0] = ce_w*CE + dice_w*dc, out[1] = CE, out[2] = dc; counts [B][C][3] = int64 (tp, fp, fn) of (z > 0) against (t > 0.5) over
+ * the valid pixels; coef: nb*c*2 + 1 floats for the backward (workspace: mia_region_loss_workspace floats, 8-byte aligned).
+ * Logits [B][C][HW] fp32 addressed by (sn, sk, sp) element strides like mia_seg_loss_fwd, 1 <= c <= 8 (c == 1 needs DO_BG).
+ * Target, dense form: contiguous planar [B][c (+1)][HW] of fp32 or, with MIA_REGLOSS_TARGET_U8, 1-byte elements (bool and uint8),
+ * values used as they are; with MIA_REGLOSS_IGNORE the extra last channel is the ignore channel, valid = (last == 0); region_bits
+ * and n_labels are not read.  Index form (MIA_REGLOSS_INDEX): a label map [B][HW] of int64 or (TARGET_U8) uint8 plus the device
+ * table region_bits[n_labels], bit c of entry l set when label l belongs to region c; with MIA_REGLOSS_IGNORE pixels labelled
+ * ignore_label are invalid; a label outside [0, n_labels) that is not the ignore label: NaN results and the sticky verdict in
+ * bad_label[1], exactly as mia_seg_loss_fwd.  pos_weight: c floats or NULL.
+ * Backward, one pass: dlogits (own strides gsn, gsk, gsp) = grad_out * valid * [ce_w (p (1 + (pw - 1) t) - pw t) / N +
+ * dice_w p (1 - p) (a t + b)] with N the divisor of CE and (a, b) from coef, both 0 where the Dice denominator was clipped; invalid
+ * pixels get exact zeros.  The index form and the dense form of the same target give bit-identical out, counts and gradients, as do
+ * the 16-byte and the scalar access paths: a thread owns the same four pixels and every sum runs in the same order in all of them.
+ * Results are bit-identical run to run (no float atomics); no host sync. */
+#define MIA_REGLOSS_DO_BG 1
+#define MIA_REGLOSS_BATCH 2
+#define MIA_REGLOSS_IGNORE 4
+#define MIA_REGLOSS_INDEX 8
+#define MIA_REGLOSS_TARGET_U8 16
+int mia_region_loss_workspace(int nb, int c, int slabs); /* floats; the buffer must be 8-byte aligned */
+int mia_region_loss_fwd(const float* logits, const void* target, const unsigned* region_bits, int n_labels, const float* pos_weight,
+                        int nb, int64_t hw, int c, int64_t sn, int64_t sk, int64_t sp, int flags, int64_t ignore_label, float smooth,
+                        float dice_w, float ce_w, int slabs, float* workspace, float* coef, float* out, int64_t* counts,
+                        int* bad_label, void* stream);
+int mia_region_loss_bwd(const float* logits, const void* target, const unsigned* region_bits, int n_labels, const float* pos_weight,
+                        const float* coef, const float* grad_out, float* dlogits, int nb, int64_t hw, int c, int64_t sn, int64_t sk,
+                        int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp, int flags, int64_t ignore_label, void* stream);
 
 /* ------------------------------------------------------------------ optimizer (al_trainer.py:1374-1379) */
 #define MIA_OPT_ADAM 0
@@ -494,6 +528,14 @@ int mia_surface_distance(const long long* pred, const long long* labels, int nvo
  * and the pointers / strides are 16-byte aligned; one pixel per thread otherwise. */
 int mia_softmax_accum(const float* logits, float* prob_sum, long long* pred, int nb, int64_t hw, int k1, int64_t sn, int64_t sk,
                       int64_t sp, float weight, int first, void* stream);
+/* The same reduction for region-based models (one sigmoid output per region, regions may overlap): prob_sum[nb][c][hw] = (first ? 0 :
+ * prob_sum) + weight * sigmoid(logits); pred != NULL also receives nnU-Net's region-to-label rule on the updated sum as int64
+ * [nb][hw]: pred = 0; for i in 0 .. c-1: if prob_sum[i] > threshold: pred = class_order[i] -- later regions overwrite earlier ones.
+ * class_order: device array of c int64 values (read only with pred).  Everything else as mia_softmax_accum: prob_sum may be NULL
+ * only with `first` set and pred given, one thread owns a pixel, models accumulate in call order, the same alignment rule decides
+ * between four pixels per thread and one; 1 <= c <= 8. */
+int mia_sigmoid_accum(const float* logits, float* prob_sum, long long* pred, const long long* class_order, int nb, int64_t hw, int c,
+                      int64_t sn, int64_t sk, int64_t sp, float weight, float threshold, int first, void* stream);
 /* Sliding-window prediction: one pass per (model, mirror combination, window).  For 0 <= i < ph, 0 <= j < pw
  *   canvas[n][k][y0+i][x0+j] += weight * gy[i] * gx[j] * softmax_k(logits[n][:, i', j']),  i' = flip_h ? ph-1-i : i, j' = flip_w ? pw-1-j : j
  * logits [nb][k1][ph][pw] fp32 addressed by (sn, sk, sp) element strides like mia_softmax_accum (pixel index i' * pw + j'), canvas

@@ -157,6 +157,146 @@ extern "C" int mia_softmax_accum(const float* logits, float* prob_sum, long long
   return MIA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ region ensemble
+// The sigmoid counterpart for region-based models (one sigmoid output per region, regions may overlap): prob_sum = (first ? 0 :
+// prob_sum) + weight * sigmoid(logits), and nnU-Net's region-to-label rule on the updated sum: pred = 0; for i in 0 .. K1-1:
+// if prob_sum[i] > threshold: pred = class_order[i] -- later regions overwrite earlier ones.  Same ownership, order and access
+// widths as softmax_accum_kernel.
+__device__ __forceinline__ float sigmoid_w(float z, float weight) {
+  const float e = __expf(-fabsf(z));  // in (0, 1]: nothing overflows
+  const float r = 1.f / (1.f + e);
+  return weight * (z >= 0.f ? r : e * r);
+}
+
+template <int K1, int MODE>
+__global__ void __launch_bounds__(256) sigmoid_accum_kernel(const float* __restrict__ logits, float* __restrict__ prob_sum,
+                                                            long long* __restrict__ pred, const long long* __restrict__ class_order,
+                                                            int64_t hw, int64_t total, int64_t sn, int64_t sk, int64_t sp, float weight,
+                                                            float threshold, int first) {
+  constexpr int PX = MODE == SA_SCALAR ? 1 : 4;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one group of PX pixels
+  if (idx >= total) return;
+  const int64_t per = hw / PX, b = idx / per, p = (idx - b * per) * PX;
+  const float* src = logits + b * sn;
+  float v[PX][K1];
+  if (MODE == SA_PLANAR4) {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(src + k * sk + p);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i][k] = t[i];
+    }
+  } else if (MODE == SA_CLAST4) {  // four pixels = K1 consecutive 16-byte units
+    float flat[4 * K1];
+#pragma unroll
+    for (int u = 0; u < K1; ++u) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(src + p * K1 + 4 * u);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) flat[4 * u + i] = t[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < K1; ++k) v[i][k] = flat[i * K1 + k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) v[0][k] = src[p * sp + k * sk];
+  }
+#pragma unroll
+  for (int i = 0; i < PX; ++i)
+#pragma unroll
+    for (int k = 0; k < K1; ++k) v[i][k] = sigmoid_w(v[i][k], weight);
+  float* acc = prob_sum ? prob_sum + (b * K1) * hw + p : nullptr;
+  if (acc && !first) {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      if (PX == 4) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(acc + k * hw);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i][k] += t[i];
+      } else {
+        v[0][k] += acc[k * hw];
+      }
+    }
+  }
+  if (acc) {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      if (PX == 4) {
+        f32x4 t;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = v[i][k];
+        store_data_fence();
+        *reinterpret_cast<f32x4*>(acc + k * hw) = t;
+        store_data_pad();  // tools/check_store_hazard.py
+      } else {
+        acc[k * hw] = v[0][k];
+      }
+    }
+  }
+  if (pred) {
+    long long order[K1], lab[PX];
+#pragma unroll
+    for (int k = 0; k < K1; ++k) order[k] = class_order[k];
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+      lab[i] = 0;
+#pragma unroll
+      for (int k = 0; k < K1; ++k) lab[i] = v[i][k] > threshold ? order[k] : lab[i];
+    }
+    long long* dst = pred + b * hw + p;
+    if (PX == 4) {
+      typedef __attribute__((ext_vector_type(2))) long long i64x2;
+      const i64x2 lo = i64x2{lab[0], lab[1]}, hi = i64x2{lab[2], lab[3]};
+      store_data_fence();
+      *reinterpret_cast<i64x2*>(dst) = lo;
+      store_data_pad();
+      *reinterpret_cast<i64x2*>(dst + 2) = hi;
+      store_data_pad();
+    } else {
+      dst[0] = lab[0];
+    }
+  }
+}
+
+template <int K1>
+static void launch_sigmoid_accum(int mode, int64_t groups, hipStream_t st, const float* logits, float* prob_sum, long long* pred,
+                                 const long long* class_order, int64_t hw, int64_t sn, int64_t sk, int64_t sp, float weight,
+                                 float threshold, int first) {
+  const dim3 grid((unsigned)ceil_div64(groups, 256)), block(256);
+#define SG_LAUNCH(M) hipLaunchKernelGGL((sigmoid_accum_kernel<K1, M>), grid, block, 0, st, logits, prob_sum, pred, class_order, hw, groups, \
+                                        sn, sk, sp, weight, threshold, first)
+  if (mode == SA_PLANAR4) SG_LAUNCH(SA_PLANAR4);
+  else if (mode == SA_CLAST4) SG_LAUNCH(SA_CLAST4);
+  else SG_LAUNCH(SA_SCALAR);
+#undef SG_LAUNCH
+}
+
+extern "C" int mia_sigmoid_accum(const float* logits, float* prob_sum, long long* pred, const long long* class_order, int nb, int64_t hw,
+                                 int c, int64_t sn, int64_t sk, int64_t sp, float weight, float threshold, int first, void* stream) {
+  MIA_CHECK_ARG(logits && nb > 0 && hw > 0, "mia_sigmoid_accum: bad arguments");
+  MIA_CHECK_ARG(c >= 1 && c <= PMAXK, "mia_sigmoid_accum: c=%d not in [1,%d]", c, PMAXK);
+  MIA_CHECK_ARG(prob_sum || (first && pred), "mia_sigmoid_accum: prob_sum may be NULL only with first set and pred given");
+  MIA_CHECK_ARG(!pred || class_order, "mia_sigmoid_accum: pred needs class_order");
+  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0, "mia_sigmoid_accum: negative strides");
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  // four pixels per thread: 16-byte aligned units in the logits, the running sum and the label map (the rule of mia_softmax_accum)
+  const bool quad = hw % 4 == 0 && al16(logits) && sn % 4 == 0 && (!prob_sum || al16(prob_sum)) && (!pred || al16(pred));
+  int mode = SA_SCALAR;
+  if (quad && sp == 1 && sk % 4 == 0) mode = SA_PLANAR4;
+  else if (quad && sk == 1 && sp == c) mode = SA_CLAST4;
+  const int64_t groups = (int64_t)nb * (mode == SA_SCALAR ? hw : hw / 4);
+  MIA_CHECK_ARG(ceil_div64(groups, 256) <= 0x7fffffffLL, "mia_sigmoid_accum: nb * hw = %lld is too large", (long long)nb * hw);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (c) {
+#define SG_CASE(K) case K: launch_sigmoid_accum<K>(mode, groups, st, logits, prob_sum, pred, class_order, hw, sn, sk, sp, weight, threshold, first); break;
+    SG_CASE(1) SG_CASE(2) SG_CASE(3) SG_CASE(4) SG_CASE(5) SG_CASE(6) SG_CASE(7) SG_CASE(8)
+#undef SG_CASE
+  }
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
 // ------------------------------------------------------------------------------------------- sliding-window prediction
 // canvas[n][k][y0 + i][x0 + j] = fma(gy[i] * gx[j], weight * softmax_k(logits[n][:, i', j']), canvas[...]) with (i', j') the
 // pixel mirrored inside the window where flip_h / flip_w say so.  Every branch below evaluates exactly that expression per

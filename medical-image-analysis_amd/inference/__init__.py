@@ -1,4 +1,5 @@
 """Prediction with trained models: the fold ensemble of the reference's `entry/fugc2025/predict.py` on the GPU, and tiled
 prediction with Gaussian blending and mirroring at the images' own resolution."""
-from .predictor import (EnsemblePredictor, ensemble_predict, sliding_window_predict, softmax_accum, window_accum,  # noqa: F401
-                        window_finalize, window_starts, window_weights)
+from .predictor import (EnsemblePredictor, ensemble_predict, ensemble_predict_regions, regions_to_labels,  # noqa: F401
+                        sigmoid_accum, sliding_window_predict, softmax_accum, window_accum, window_finalize, window_starts,
+                        window_weights)

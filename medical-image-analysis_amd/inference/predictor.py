@@ -98,6 +98,94 @@ def ensemble_predict(models: Sequence[torch.nn.Module], x: torch.Tensor, weights
     return (pred, prob_sum) if return_probs else pred
 
 
+def regions_to_labels(prob_sum: torch.Tensor, class_order, threshold: float) -> torch.Tensor:
+    """nnU-Net's region-to-label rule in torch ops: ``pred = 0; for i: pred[prob_sum[:, i] > threshold] = class_order[i]`` --
+    later regions overwrite earlier ones.  [B,C,H,W] -> int64 [B,H,W]; the definition `mia_sigmoid_accum` follows."""
+    pred = torch.zeros((prob_sum.shape[0],) + tuple(prob_sum.shape[2:]), dtype=torch.int64, device=prob_sum.device)
+    for i, lab in enumerate(class_order):
+        pred[prob_sum[:, i] > threshold] = int(lab)
+    return pred
+
+
+def sigmoid_accum(logits: torch.Tensor, prob_sum: Optional[torch.Tensor], pred: Optional[torch.Tensor],
+                  class_order: Optional[torch.Tensor] = None, weight: float = 1.0, threshold: float = 0.5, first: bool = False) -> None:
+    """``prob_sum = (0 if first else prob_sum) + weight * logits.sigmoid()`` in place, and where ``pred`` is given the
+    region-to-label rule on the updated sum (`regions_to_labels` with ``class_order``, a device int64 tensor of C labels).
+    logits [B,C,H,W] fp32 on the GPU, any strides whose H and W collapse (the head's channels-last view included); prob_sum
+    contiguous [B,C,H,W] fp32 or None (only with ``first`` and ``pred``); pred contiguous [B,H,W] int64 or None."""
+    from mia_hip import call
+    from mia_hip.ops import _c_i64, _need_dev, _p, _pix_strides, _stream
+    _need_dev(logits, prob_sum, pred, class_order)
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    st = _pix_strides(logits)
+    if st is None:
+        logits = logits.contiguous()
+        st = _pix_strides(logits)
+    b, c, h, w = logits.shape
+    if prob_sum is not None and not (prob_sum.dtype == torch.float32 and prob_sum.is_contiguous() and prob_sum.shape == logits.shape):
+        raise ValueError("prob_sum must be a contiguous fp32 tensor of the logits' shape")
+    if pred is not None:
+        if not (pred.dtype == torch.int64 and pred.is_contiguous() and tuple(pred.shape) == (b, h, w)):
+            raise ValueError("pred must be a contiguous int64 tensor [B,H,W]")
+        if class_order is None or not (class_order.dtype == torch.int64 and class_order.is_contiguous() and class_order.numel() == c):
+            raise ValueError(f"class_order must be a contiguous int64 tensor of {c} labels")
+    call("mia_sigmoid_accum", _p(logits), _p(prob_sum), _p(pred), _p(class_order), b, _c_i64(h * w), c, _c_i64(st[0]), _c_i64(st[1]),
+         _c_i64(st[2]), ctypes.c_float(float(weight)), ctypes.c_float(float(threshold)), int(bool(first)), _stream())
+
+
+def ensemble_predict_regions(models: Sequence[torch.nn.Module], x: torch.Tensor, class_order: Sequence[int],
+                             weights: Optional[Sequence[float]] = None, return_probs: bool = False):
+    """Label map [B,H,W] (int64) of region-based models: ``prob_sum = sum_m weights[m] * models[m](x).sigmoid()`` and then
+    `regions_to_labels(prob_sum, class_order, 0.5 * sum(weights))`, i.e. the mean probability thresholded at 1/2 and the regions
+    written in order, later ones over earlier ones (``class_order[i]`` is the label of output channel i).
+
+    Like `ensemble_predict`: every model runs in eval mode under ``torch.no_grad()`` and gets its train / eval mode back on every
+    exit path; models are accumulated in order with one logits tensor alive at a time; bit-identical from run to run; CPU logits
+    take the same definition in torch ops.  ``return_probs=True`` returns ``(labels, prob_sum [B,C,H,W] fp32)``."""
+    models = list(models)
+    if not models:
+        raise ValueError("ensemble_predict_regions needs at least one model")
+    weights = [1.0] * len(models) if weights is None else [float(v) for v in weights]
+    if len(weights) != len(models):
+        raise ValueError(f"{len(weights)} weights for {len(models)} models")
+    class_order = [int(v) for v in class_order]
+    threshold = 0.5 * sum(weights)
+    modes = [m.training for m in models]
+    prob_sum = pred = order = None
+    try:
+        for m in models:
+            m.eval()
+        with torch.no_grad():
+            for i, (m, wt) in enumerate(zip(models, weights)):
+                logits = _logits_of(m, x)
+                if logits.dim() != 4:
+                    raise ValueError(f"model {i} returned shape {tuple(logits.shape)}; expected logits [B,C,H,W]")
+                if logits.shape[1] != len(class_order):
+                    raise ValueError(f"model {i} has {logits.shape[1]} output channels, class_order names {len(class_order)} regions")
+                last = i == len(models) - 1
+                if logits.is_cuda:
+                    b, c, h, w = logits.shape
+                    if prob_sum is None and (len(models) > 1 or return_probs):
+                        prob_sum = torch.empty((b, c, h, w), device=logits.device, dtype=torch.float32)
+                    if last:
+                        pred = torch.empty((b, h, w), device=logits.device, dtype=torch.int64)
+                        order = torch.tensor(class_order, dtype=torch.int64, device=logits.device)
+                    if prob_sum is not None and tuple(prob_sum.shape) != tuple(logits.shape):
+                        raise ValueError(f"model {i} returned shape {tuple(logits.shape)}, the models before it {tuple(prob_sum.shape)}")
+                    sigmoid_accum(logits, prob_sum, pred, order, wt, threshold, first=i == 0)
+                else:  # the same definition in torch ops
+                    p = wt * logits.float().sigmoid()
+                    prob_sum = p if prob_sum is None else prob_sum + p
+                    if last:
+                        pred = regions_to_labels(prob_sum, class_order, threshold)
+                del logits
+    finally:
+        for m, was in zip(models, modes):
+            m.train(was)
+    return (pred, prob_sum) if return_probs else pred
+
+
 def window_starts(n: int, p: int, overlap: float) -> list:
     """Start offsets of windows of length ``p`` that cover ``n`` pixels with at least ``overlap`` (a fraction of ``p``) between
     neighbours: ``k = ceil((n - p) / (p * (1 - overlap))) + 1`` windows spread evenly, the first at 0 and the last at ``n - p``."""

@@ -64,7 +64,8 @@ def _index_labels(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 class MemoryEfficientSoftDiceLoss(nn.Module):
     """-mean Dice with the denominator clipped at 1e-8 (reference `dice_loss.py:100-165`), on the fused kernel.
-    `apply_nonlin` is `softmax_helper_dim1` (soft-max in the kernel) or None (logits used as they are)."""
+    `apply_nonlin` is `softmax_helper_dim1` (soft-max in the kernel) or None (logits used as they are), both with index labels;
+    or `torch.sigmoid` with a dense (multi-label) target of the input's shape -- the region-based mode, on the region kernel."""
 
     def __init__(self, apply_nonlin: Callable | None = None, batch_dice: bool = False, do_bg: bool = True, smooth: float = 1.0):
         super().__init__()
@@ -76,10 +77,36 @@ class MemoryEfficientSoftDiceLoss(nn.Module):
     def _flags(self) -> int:
         if self.apply_nonlin is not None and self.apply_nonlin is not softmax_helper_dim1:
             raise NotImplementedError("MemoryEfficientSoftDiceLoss on the HIP kernel: apply_nonlin must be "
-                                      "losses.compound_losses.softmax_helper_dim1 or None")
+                                      "losses.compound_losses.softmax_helper_dim1 or None (index labels), or torch.sigmoid with a "
+                                      "dense target of the input's shape")
         return ops.seg_loss_flags(self.apply_nonlin is not None, self.do_bg, self.batch_dice)
 
+    def _region_flags(self, x: torch.Tensor) -> int:
+        """Checks and kernel flags of the sigmoid (region) mode."""
+        if x.ndim != 4:
+            raise NotImplementedError("the HIP segmentation losses implement 2-D inputs [B, C, H, W]")
+        if x.shape[1] > ops.REGLOSS_MAX_CHANNELS:
+            raise NotImplementedError(f"the HIP region loss implements up to {ops.REGLOSS_MAX_CHANNELS} channels, got {x.shape[1]}")
+        if x.shape[1] == 1 and not self.do_bg:
+            raise ValueError("one output channel with do_bg=False leaves no Dice term")
+        return ops.region_loss_flags(self.do_bg, self.batch_dice)
+
+    def _forward_sigmoid(self, x: torch.Tensor, y: torch.Tensor, loss_mask):
+        flags = self._region_flags(x)
+        ops._need_dev(x, y, loss_mask)
+        if loss_mask is not None:  # the kernel's ignore channel is the complement of the mask, in the target's own dtype
+            b, _, h, w = x.shape
+            if loss_mask.numel() != b * h * w:
+                raise AssertionError("inputs {} & loss_mask {} shape do not match".format(tuple(x.shape), tuple(loss_mask.shape)))
+            if y.dtype not in (torch.bool, torch.uint8, torch.float32):
+                y = y.float()
+            y = torch.cat((y, (loss_mask.reshape(b, 1, h, w) == 0).to(y.dtype)), 1)
+            flags |= ops.REGLOSS_IGNORE
+        return ops.RegionLossFn.apply(x, y, None, None, flags, None, float(self.smooth), 1.0, 0.0, 2)
+
     def forward(self, x: torch.Tensor, y: torch.Tensor, loss_mask: torch.Tensor | None = None):
+        if self.apply_nonlin is torch.sigmoid and y.shape == x.shape:  # equal shapes = dense target, for one channel too
+            return self._forward_sigmoid(x, y, loss_mask)
         flags = self._flags()
         lab = _index_labels(x, y)
         ops._need_dev(x, y, loss_mask)

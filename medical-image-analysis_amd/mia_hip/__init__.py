@@ -22,6 +22,7 @@ WGRAD_3S1, WGRAD_3S2, WGRAD_2S2 = range(3)
 NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_SOFTMAX, LOSS_DO_BG, LOSS_BATCH, LOSS_SQUARED, LOSS_DENSE = 1, 2, 4, 8, 16
 SEGLOSS_SOFTMAX, SEGLOSS_DO_BG, SEGLOSS_BATCH, SEGLOSS_LABEL_U8, SEGLOSS_IGNORE = 1, 2, 4, 8, 16
+REGLOSS_DO_BG, REGLOSS_BATCH, REGLOSS_IGNORE, REGLOSS_INDEX, REGLOSS_TARGET_U8 = 1, 2, 4, 8, 16
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 
 

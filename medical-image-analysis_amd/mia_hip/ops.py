@@ -14,7 +14,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import (BF16, CONV_G1, CONV_G2S2, CONV_G3S1, CONV_G3S2, CONV_T2S2, CONV_T3S2, F32, LOSS_BATCH, LOSS_DO_BG,
-               LOSS_DENSE, LOSS_SOFTMAX, LOSS_SQUARED, NORM_BATCH, NORM_INSTANCE, SEGLOSS_BATCH, SEGLOSS_DO_BG, SEGLOSS_IGNORE,
+               LOSS_DENSE, LOSS_SOFTMAX, LOSS_SQUARED, NORM_BATCH, NORM_INSTANCE, REGLOSS_BATCH, REGLOSS_DO_BG, REGLOSS_IGNORE,
+               REGLOSS_INDEX, REGLOSS_TARGET_U8, SEGLOSS_BATCH, SEGLOSS_DO_BG, SEGLOSS_IGNORE,
                SEGLOSS_LABEL_U8, SEGLOSS_SOFTMAX, WGRAD_2S2, WGRAD_3S1, WGRAD_3S2, MiaError, call, lib)
 
 LRELU_SLOPE = 0.01
@@ -1374,6 +1375,117 @@ class TopKCEFn(torch.autograd.Function):
 
 
 TopKCEFn.last_threshold = None
+
+
+# ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
+REGLOSS_MAX_CHANNELS = 8
+
+
+def region_loss_flags(do_bg: bool, batch: bool) -> int:
+    return (REGLOSS_DO_BG if do_bg else 0) | (REGLOSS_BATCH if batch else 0)
+
+
+def region_bits(regions, device) -> torch.Tensor:
+    """Device table for the index form: entry l (int32, read as uint32) has bit c set when label l belongs to `regions[c]`."""
+    regions = [tuple(int(v) for v in r) for r in regions]
+    if not 1 <= len(regions) <= REGLOSS_MAX_CHANNELS:
+        raise NotImplementedError(f"the HIP region loss implements 1..{REGLOSS_MAX_CHANNELS} regions, got {len(regions)}")
+    if any(v < 0 for r in regions for v in r):
+        raise ValueError("regions: labels must be >= 0")
+    n = max((v for r in regions for v in r), default=0) + 1
+    bits = [0] * n
+    for c, r in enumerate(regions):
+        for v in r:
+            bits[v] |= 1 << c
+    return torch.tensor(bits, dtype=torch.int32, device=device)
+
+
+class RegionLossFn(torch.autograd.Function):
+    """ce_w * BCEWithLogits(pos_weight) + dice_w * MemoryEfficientSoftDice(sigmoid) over the valid pixels in one pass over the logits
+    (src/losses/compound_losses.py:178-233), plus the hard tp / fp / fn of (logit > 0) against (target > 0.5).  `target` is dense
+    [B,C,H,W] (or [B,C+1,H,W] with REGLOSS_IGNORE: the last channel marks ignored pixels) in bool, uint8 or fp32 -- handed to the
+    kernel as it is -- or, with a `bits` table (`region_bits`), a label map [B,H,W] in uint8 or int64 whose `ignore_label` pixels are
+    invalid.  `which` picks the returned scalar: 0 total, 1 ce, 2 dc; the other two and the counts of the latest forward stay
+    readable as `RegionLossFn.last_out` ([3] fp32) and `RegionLossFn.last_counts` ([B,C,3] int64)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, bits, pos_weight, flags: int, ignore_label, smooth: float, dice_w: float, ce_w: float, which: int):
+        _need_dev(logits, target, bits, pos_weight)
+        if logits.ndim != 4:
+            raise NotImplementedError("the HIP region loss implements 2-D inputs [B, C, H, W]")
+        if logits.dtype != torch.float32:
+            logits = logits.float()
+        st = _pix_strides(logits)
+        if st is None:
+            logits = logits.contiguous()
+            st = _pix_strides(logits)
+        b, c, h, w = logits.shape
+        if c > REGLOSS_MAX_CHANNELS:
+            raise NotImplementedError(f"the HIP region loss implements up to {REGLOSS_MAX_CHANNELS} channels, got {c}")
+        flags &= REGLOSS_DO_BG | REGLOSS_BATCH | REGLOSS_IGNORE
+        n_labels, ign = 0, 0
+        if bits is not None:
+            flags |= REGLOSS_INDEX
+            if target.numel() != b * h * w:
+                raise MiaError(f"labels {tuple(target.shape)} do not index the pixels of logits {tuple(logits.shape)}")
+            target = target.reshape(b, h, w)
+            if target.dtype == torch.uint8:
+                flags |= REGLOSS_TARGET_U8
+            elif target.dtype != torch.long:
+                target = target.long()
+            bits = bits.to(device=logits.device, dtype=torch.int32).contiguous()
+            n_labels = bits.numel()
+            if ignore_label is not None:
+                flags |= REGLOSS_IGNORE
+                ign = int(ignore_label)
+        else:
+            ct = c + (1 if flags & REGLOSS_IGNORE else 0)
+            if tuple(target.shape) != (b, ct, h, w):
+                raise MiaError(f"dense target {tuple(target.shape)} for logits {tuple(logits.shape)}: expected {(b, ct, h, w)}")
+            if target.dtype in (torch.bool, torch.uint8):
+                flags |= REGLOSS_TARGET_U8
+            elif target.dtype != torch.float32:
+                target = target.float()
+        target = target.contiguous()
+        if pos_weight is not None:
+            if pos_weight.numel() != c:
+                raise MiaError(f"pos_weight: {pos_weight.numel()} values for {c} channels")
+            pos_weight = pos_weight.detach().to(device=logits.device, dtype=torch.float32).reshape(c).contiguous()
+        hw = h * w
+        slabs = max(1, min(256, hw // 8192))
+        dev = logits.device
+        ws = torch.empty((lib().mia_region_loss_workspace(b, c, slabs) + 1) // 2, device=dev, dtype=torch.float64)  # 8-byte aligned
+        coef = torch.empty(b * c * 2 + 1, device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
+        out = torch.empty(3, device=dev, dtype=torch.float32)
+        counts = torch.empty((b, c, 3), device=dev, dtype=torch.int64)
+        bad = _bad_flags(dev)
+        call("mia_region_loss_fwd", _p(logits), _p(target), _p(bits), n_labels, _p(pos_weight), b, _c_i64(hw), c, _c_i64(st[0]),
+             _c_i64(st[1]), _c_i64(st[2]), flags, _c_i64(ign), _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws),
+             _p(coef), _p(out), _p(counts), _p(bad), _stream())
+        ctx.save_for_backward(logits, target, coef)
+        ctx.bits, ctx.pos_weight = bits, pos_weight
+        ctx.flags, ctx.ign, ctx.st, ctx.n_labels = flags, ign, st, n_labels
+        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
+        RegionLossFn.last_out = out
+        RegionLossFn.last_counts = counts
+        return out[which]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, coef = ctx.saved_tensors
+        b, c, h, w = logits.shape
+        dl = torch.empty_like(logits)  # preserves (dense) strides
+        gst = _pix_strides(dl)
+        g = gout.reshape(1).float().contiguous()
+        st = ctx.st
+        call("mia_region_loss_bwd", _p(logits), _p(target), _p(ctx.bits), ctx.n_labels, _p(ctx.pos_weight), _p(coef), _p(g), _p(dl), b,
+             _c_i64(h * w), c, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags,
+             _c_i64(ctx.ign), _stream())
+        return dl, None, None, None, None, None, None, None, None, None
+
+
+RegionLossFn.last_out = None
+RegionLossFn.last_counts = None
 
 
 def hard_tp_fp_fn(logits: torch.Tensor, target: torch.Tensor, ignore_label=None) -> torch.Tensor:
