@@ -315,6 +315,20 @@ int mia_dice_ce_bwd(const float* logits, const long long* labels, const float* c
                     int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp,
                     int flags, float dice_w, float ce_w, void* stream);
 
+/* Deep supervision: the same Dice + CE of an auxiliary head's LOW-resolution logits z [nb][k1][h*w] (element strides sn, sk, sp as above)
+ * against FULL-resolution int64 labels [nb][H*W], H = h*factor, W = w*factor, factor in {2, 4, 8, 16}, k1 in 1..8.  The logits are
+ * upsampled in registers, u = Uy z Ux^T with U = torch interpolate(scale_factor=factor, mode="bilinear", align_corners=False); the loss is
+ * what mia_dice_ce_fwd computes on u (same sums, coef, out, bad_label protocol; MIA_LOSS_DENSE is refused), and the backward writes
+ * dz = Uy^T du Ux (du = what mia_dice_ce_bwd would write for u) by gather through dz's own strides (gsn, gsk, gsp).  Neither u nor du is
+ * ever stored.  No float atomics: out, sums and dz are bit-identical run to run; no host sync. */
+int mia_ds_loss_workspace(int nb, int k1, int slabs); /* floats */
+int mia_ds_loss_fwd(const float* z, const long long* labels, int nb, int h, int w, int factor, int k1, int64_t sn, int64_t sk,
+                    int64_t sp, int flags, float smooth, float dice_w, float ce_w, int slabs, float* workspace, float* sums,
+                    float* coef, float* out, int* bad_label, void* stream);
+int mia_ds_loss_bwd(const float* z, const long long* labels, const float* coef, const float* grad_out, float* dz, int nb, int h,
+                    int w, int factor, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp, int flags,
+                    float dice_w, float ce_w, void* stream);
+
 /* Head fused with the last decoder block (unet.py:176 behind blocks.py:98-100): the block's activation
  * z = lrelu(scale*y + shift) has one consumer, the 1x1 head, so it is never materialised -- the head recomputes it from the
  * raw conv output y on load, and the block's norm backward recomputes dz = W^T dlogits instead of reading it.

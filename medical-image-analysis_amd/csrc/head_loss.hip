@@ -972,6 +972,15 @@ __global__ void dice_ce_finalize_kernel(const float* __restrict__ part, const fl
   }
 }
 
+// The finalize launch for other files that produce the same `part` / `cepart` layout (ds_loss.hip).
+int mia_dice_ce_finalize_launch(const float* part, const float* cepart, int nb, int slabs, int k1, int64_t hw, int flags, float smooth,
+                                float dice_w, float ce_w, float* sums, float* coef, float* out, int* bad_label, hipStream_t st) {
+  hipLaunchKernelGGL(dice_ce_finalize_kernel, dim3(1), dim3(256), 0, st, part, cepart, nb, slabs, k1, hw, flags, smooth, dice_w, ce_w, sums,
+                     coef, out, bad_label);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
 // backward: dlogits[b,p,k] = gout * ( ce_w/(B*HW) * (softmax_k - t_k) + dice_w * dDice/dlogit_k )
 __global__ void dice_ce_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
                                    const float* __restrict__ coef, const float* __restrict__ gout, float* __restrict__ dl,

@@ -1249,6 +1249,65 @@ def check_labels() -> None:
                        "the reference raises an index error for such targets")
 
 
+DS_LOSS_FACTORS = (2, 4, 8, 16)
+DS_LOSS_MAX_CLASSES = 8
+
+
+class UpsampleDiceCEFn(torch.autograd.Function):
+    """DiceCEFn on bilinearly upsampled logits (`Upsample(scale_factor=factor, mode="bilinear", align_corners=False)`, the
+    deep-supervision heads of unet.py:193-197) without the upsampled tensor: the forward interpolates the low-resolution logits in
+    registers, the backward gathers d loss / d z_lowres directly.  Index labels [B,H*factor,W*factor] only."""
+
+    @staticmethod
+    def forward(ctx, z, labels, factor: int, flags: int, smooth: float, dice_w: float, ce_w: float, which: int):
+        _need_dev(z, labels)
+        if z.dtype != torch.float32:
+            z = z.float()
+        st = _pix_strides(z)
+        if st is None:
+            z = z.contiguous()
+            st = _pix_strides(z)
+        b, k1, h, w = z.shape
+        factor = int(factor)
+        if factor not in DS_LOSS_FACTORS or not 1 <= k1 <= DS_LOSS_MAX_CLASSES:
+            raise MiaError(f"UpsampleDiceCEFn: factor {factor} / {k1} classes not supported (factors {DS_LOSS_FACTORS}, up to "
+                           f"{DS_LOSS_MAX_CLASSES} classes)")
+        if flags & LOSS_DENSE or labels.numel() != b * h * factor * w * factor:
+            raise MiaError(f"UpsampleDiceCEFn: index labels of {b}x{h * factor}x{w * factor} pixels expected, got {tuple(labels.shape)}")
+        labels = labels.reshape(b, h * factor, w * factor)
+        if labels.dtype != torch.long:
+            labels = labels.long()
+        labels = labels.contiguous()
+        hw = h * factor * w * factor
+        slabs = max(1, min(256, hw // 8192))
+        dev = z.device
+        ws = torch.empty(lib().mia_ds_loss_workspace(b, k1, slabs), device=dev, dtype=torch.float32)
+        sums = torch.empty((b, k1, 3), device=dev, dtype=torch.float32)
+        coef = torch.empty((b, k1, 2), device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
+        out = torch.empty(3, device=dev, dtype=torch.float32)
+        bad = _bad_flags(dev)
+        call("mia_ds_loss_fwd", _p(z), _p(labels), b, h, w, factor, k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), flags,
+             _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(sums), _p(coef), _p(out), _p(bad), _stream())
+        ctx.save_for_backward(z, labels, coef)
+        ctx.factor, ctx.flags, ctx.dice_w, ctx.ce_w, ctx.st = factor, flags, dice_w, ce_w, st
+        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
+        DiceCEFn.last_sums = sums
+        return out[which]
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, labels, coef = ctx.saved_tensors
+        b, k1, h, w = z.shape
+        dz = torch.empty_like(z)  # preserves (dense) strides
+        gst = _pix_strides(dz)
+        g = gout.reshape(1).float().contiguous()
+        st = ctx.st
+        call("mia_ds_loss_bwd", _p(z), _p(labels), _p(coef), _p(g), _p(dz), b, h, w, ctx.factor, k1, _c_i64(st[0]), _c_i64(st[1]),
+             _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_float(ctx.dice_w), _c_float(ctx.ce_w),
+             _stream())
+        return dz, None, None, None, None, None, None, None
+
+
 # ------------------------------------------------------------------ fold-trainer losses (masked soft Dice + CE, top-k CE)
 def seg_loss_flags(softmax: bool, do_bg: bool, batch: bool) -> int:
     return (SEGLOSS_SOFTMAX if softmax else 0) | (SEGLOSS_DO_BG if do_bg else 0) | (SEGLOSS_BATCH if batch else 0)

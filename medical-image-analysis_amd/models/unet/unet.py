@@ -125,8 +125,9 @@ class UNetDecoder(nn.Module):
                     ds = None
                 self.ds.append(ds)
 
-    def _run(self, skips, return_ds, fuse_head=False):
-        """skips: NHWC tensors, encoder order (bottleneck last)."""
+    def _run(self, skips, return_ds, fuse_head=False, upsample_ds=True):
+        """skips: NHWC tensors, encoder order (bottleneck last).  upsample_ds=False: the auxiliary heads' logits stay at their
+        own resolution (the 1x1 conv of `self.ds[l]` without its `Upsample`), for losses that upsample on the fly."""
         skips = list(skips)[::-1]
         x = skips.pop(0)
         ds_feats, ds_outputs = [], []
@@ -146,19 +147,20 @@ class UNetDecoder(nn.Module):
             if return_ds and self.deep_supervision and (l in self.ds_layer_list):
                 head = self.ds[l][0]
                 ds_feats.append(x)
-                ds_outputs.append(self.ds[l][1](ops.HeadFn.apply(x, head.weight, head.bias)))
+                low = ops.HeadFn.apply(x, head.weight, head.bias)
+                ds_outputs.append(self.ds[l][1](low) if upsample_ds else low)
         seg = ops.HeadFn.apply(x, self.seg_output.weight, self.seg_output.bias)
         return seg, x, ds_outputs, ds_feats
 
-    def forward_nhwc(self, skips, return_ds=False):
-        seg, _, ds_outputs, _ = self._run(skips, return_ds, fuse_head=True)
+    def forward_nhwc(self, skips, return_ds=False, upsample_ds=True):
+        seg, _, ds_outputs, _ = self._run(skips, return_ds, fuse_head=True, upsample_ds=upsample_ds)
         if return_ds:
             return [seg] + ds_outputs[::-1]
         return seg
 
-    def forward(self, skips, return_ds=False):
+    def forward(self, skips, return_ds=False, upsample_ds=True):
         dt = _compute_dtype(self, skips[0])
-        return self.forward_nhwc([ops.to_nhwc(s, dt) for s in skips], return_ds)
+        return self.forward_nhwc([ops.to_nhwc(s, dt) for s in skips], return_ds, upsample_ds)
 
     def get_feature_nhwc(self, skips, return_ds=False):
         seg, x, ds_outputs, ds_feats = self._run(skips, return_ds)
@@ -215,12 +217,14 @@ class UNet(nn.Module):
             b._drop_from_pool = pool[off:off + sz].view(n, -1)
             off += sz
 
-    def forward(self, x, return_ds=False):
+    def forward(self, x, return_ds=False, upsample_ds=True):
+        """return_ds: [main logits] + the auxiliary heads' outputs, finest first; with upsample_ds=False those stay at their own
+        (lower) resolution, which is what `losses.deep_supervision.DeepSupervisionLoss` takes."""
         ops._COLSUM_HINT.clear()  # hints are only valid inside the backward pass of the forward that produced them
         ops._ACC_HINT.clear()
         ops._CR_HINT.clear()
         self._draw_dropout(x.shape[0], x.device)
-        return self.decoder.forward_nhwc(self._skips(x), return_ds=return_ds)
+        return self.decoder.forward_nhwc(self._skips(x), return_ds=return_ds, upsample_ds=upsample_ds)
 
     def get_enc_feature(self, x):
         return ops.global_avg_pool(self._skips(x)[-1])

@@ -306,8 +306,12 @@ class TrainEngine:
                  start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
                  lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None, bucket_bytes: int = 16 << 20,
                  sync_batchnorm: Optional[bool] = None, force_reducer: bool = False, dp_reserve_cus: Optional[int] = None,
-                 graph: Optional[bool] = None):
+                 graph: Optional[bool] = None, deep_supervision: bool = False):
         """force_reducer: see GradBucketReducer(force=...).
+        deep_supervision: train the decoder's auxiliary heads (`UNet(deep_supervision=True, ds_layer=n)`) as well: the step calls
+        `model(image, return_ds=True, upsample_ds=False)` and a plain `loss_fn` is wrapped in
+        `losses.deep_supervision.DeepSupervisionLoss` with its default weights (a DeepSupervisionLoss is taken as it is); the returned
+        loss is the weighted total.  Needs a model whose decoder has such heads.
         graph: replay the whole step (forward, loss, backward, clip, optimizer, weight re-pack) from ONE captured hipGraph
         (`torch.cuda.CUDAGraph`) after `GRAPH_WARMUP` eager steps -- for small models whose step is launch-bound (cfg1: ~117
         launches for 1.1 ms of kernels).  Same kernels, same order, same arithmetic as the eager step: the values that change per
@@ -331,6 +335,15 @@ class TrainEngine:
         than one rank, so N ranks x bs reproduce one process at N*bs (`normalization="batch"` is the al_train
         default, train.py:25); False keeps per-rank statistics (DDP-without-SyncBN behaviour) and says so once."""
         self.model = model
+        self.deep_supervision = bool(deep_supervision)
+        if self.deep_supervision:
+            heads = getattr(getattr(model, "decoder", None), "ds", None)
+            if heads is None or all(h is None for h in heads):
+                raise ValueError("TrainEngine(deep_supervision=True) needs a model whose decoder has auxiliary heads "
+                                 "(UNet(deep_supervision=True, ds_layer >= 2))")
+            from losses.deep_supervision import DeepSupervisionLoss
+            if not isinstance(loss_fn, DeepSupervisionLoss):
+                loss_fn = DeepSupervisionLoss(loss_fn)
         world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         if dp_reserve_cus is None:
             dp_reserve_cus = DP_RESERVE_CUS if world > 1 else None
@@ -380,6 +393,11 @@ class TrainEngine:
         self._graph_epoch = None  # ops.PARAM_EPOCH as the last capture / replay left it
         self._feed = None  # training.feed.HostFeed, created by the first batch that arrives in host memory
 
+    def _forward(self, image: torch.Tensor):
+        if self.deep_supervision:
+            return self.model(image, return_ds=True, upsample_ds=False)
+        return self.model(image)
+
     GRAPH_WARMUP = 3  # eager steps before capture: lazy module loads, PackPlan creation (step 2), allocator warm-up
 
     def _capture(self, image: torch.Tensor, label: torch.Tensor) -> "_CapturedStep":
@@ -401,7 +419,7 @@ class TrainEngine:
         self.reducer.suspended = True
         try:
             with torch.cuda.graph(g.graph, capture_error_mode="thread_local"):
-                output = self.model(g.img)
+                output = self._forward(g.img)
                 loss = self.loss_fn(output, g.lab)
                 opt.zero_grad()
                 loss.backward(self._one if self._one.shape == loss.shape else torch.ones_like(loss))
@@ -503,7 +521,7 @@ class TrainEngine:
             ev0 = torch.cuda.Event(enable_timing=True)
             ev0.record()
             t_host = time.perf_counter()
-        output = self.model(image)
+        output = self._forward(image)
         loss = self.loss_fn(output, label)
         self.optimizer.zero_grad()
         self.reducer.start_step()
