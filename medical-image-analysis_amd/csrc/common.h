@@ -180,6 +180,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // Block-wide sum for blockDim.x <= 1024 (multiple of 64); result valid in thread 0.
 __device__ __forceinline__ float block_sum(float v, float* red /*>= 16 floats LDS*/) {
   v = wave_sum(v);

@@ -14,19 +14,9 @@
 // is computed ONCE per pixel into LDS, (2) reduced along x with the column weights, (3) reduced along y with the row weights, and
 // written through dz's own strides.  Every sum runs in a fixed order and there is no atomic anywhere: out, sums and dz are
 // bit-identical run to run.  Nothing synchronises with the host; every launch goes to the caller's stream.
-#include "common.h"
+#include "loss_common.h"
 
-#define DS_MAXK 8
-#define DS_SOFTMAX 1  // the MIA_LOSS_* bits this file looks at itself; the finalize kernel reads the rest
-#define DS_SQUARED 8
-#define DS_DENSE 16
 #define DS_LDS_BYTES (60 * 1024)  // per block: below the 64 KiB a kernel gets without asking, two or more blocks per CU
-
-struct DsGeom { int64_t sn, sk, sp; };  // element strides of a logits-shaped tensor: image, class, pixel
-
-// head_loss.hip: launches dice_ce_finalize_kernel on `part` [B][slabs][K1][3] / `cepart` [B][slabs]
-int mia_dice_ce_finalize_launch(const float* part, const float* cepart, int nb, int slabs, int k1, int64_t hw, int flags, float smooth,
-                                float dice_w, float ce_w, float* sums, float* coef, float* out, int* bad_label, hipStream_t st);
 
 // source taps of full-resolution index `dst` on an axis of n low-resolution pixels (scale = 1 / factor, exact)
 struct DsTap { int i0, i1; float l; };
@@ -44,7 +34,7 @@ __device__ __forceinline__ float ds_weight(const DsTap& t, int i) { return (t.i0
 
 // u[k] = bilinear(z)[k] at one full-resolution pixel; zb = the image's logits
 template <int NK>
-__device__ __forceinline__ void ds_interp(const float* __restrict__ zb, const DsGeom& g, int w, int k1, const DsTap& ty, const DsTap& tx,
+__device__ __forceinline__ void ds_interp(const float* __restrict__ zb, const LossGeom& g, int w, int k1, const DsTap& ty, const DsTap& tx,
                                           float (&v)[NK]) {
   const int64_t o00 = ((int64_t)ty.i0 * w + tx.i0) * g.sp, o01 = ((int64_t)ty.i0 * w + tx.i1) * g.sp;
   const int64_t o10 = ((int64_t)ty.i1 * w + tx.i0) * g.sp, o11 = ((int64_t)ty.i1 * w + tx.i1) * g.sp;
@@ -64,11 +54,9 @@ __device__ __forceinline__ void ds_interp(const float* __restrict__ zb, const Ds
 // NK: compile-time class bound (k1 == NK for 2, 3, 4; NK = 8 with a run-time k1 otherwise).  VEC: two pixels per 16-byte label load.
 template <int NK, bool VEC>
 __global__ __launch_bounds__(256) void ds_loss_fwd_kernel(const float* __restrict__ z, const long long* __restrict__ labels, int h, int w,
-                                                          int factor, int k1, DsGeom g, int flags, int slabs, float* __restrict__ part,
+                                                          int factor, int k1, LossGeom g, int flags, int slabs, float* __restrict__ part,
                                                           float* __restrict__ cepart, int* __restrict__ bad_label) {
-  constexpr int NV = 3 * NK + 1;
   constexpr int PX = VEC ? 2 : 1;
-  __shared__ float red[4][NV];
   const int b = blockIdx.x / slabs, s = blockIdx.x % slabs;
   const int H = h * factor, W = w * factor;
   const int per = (H + slabs - 1) / slabs;
@@ -86,8 +74,7 @@ __global__ __launch_bounds__(256) void ds_loss_fwd_kernel(const float* __restric
     const DsTap ty = ds_tap(yy, scale, h);
     unsigned lo[PX], hi[PX];
     if constexpr (VEC) {
-      const u32x4 l = *reinterpret_cast<const u32x4*>(lb + (size_t)yy * W + x);
-      lo[0] = l[0]; hi[0] = l[1]; lo[PX - 1] = l[2]; hi[PX - 1] = l[3];
+      load_label_pair(lb + (size_t)yy * W + x, lo, hi);
     } else {
       const unsigned long long l = (unsigned long long)lb[(size_t)yy * W + x];
       lo[0] = (unsigned)(l & 0xFFFFFFFFull); hi[0] = (unsigned)(l >> 32);
@@ -112,29 +99,29 @@ __global__ __launch_bounds__(256) void ds_loss_fwd_kernel(const float* __restric
 #pragma unroll
       for (int k = 0; k < NK; ++k)
         if (k < k1) {
-          const float pk = (flags & DS_SOFTMAX) ? pr[k] * inv : (ok ? v[k] : 0.f);
+          const float pk = (flags & LF_SOFTMAX) ? pr[k] * inv : (ok ? v[k] : 0.f);
           const float t = (ok && lo[j] == (unsigned)k) ? 1.f : 0.f;
           si[k] += pk * t;
-          sp[k] += (flags & DS_SQUARED) ? pk * pk : pk;
+          sp[k] += (flags & LF_SQUARED) ? pk * pk : pk;
           st[k] += t;
           ce += t * (lse - v[k]);
         }
     }
   }
   if (bad) *bad_label = 1;
-  const int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+  auto red = loss_block_sums<3 * NK + 1, 0>();
 #pragma unroll
   for (int k = 0; k < NK; ++k)
     if (k < k1) {
-      const float a = wave_sum(si[k]), c = wave_sum(sp[k]), d = wave_sum(st[k]);
-      if (l == 0) { red[wv][3 * k] = a; red[wv][3 * k + 1] = c; red[wv][3 * k + 2] = d; }
+      const float v[3] = {si[k], sp[k], st[k]};
+      red.put(3 * k, v);
     }
-  ce = wave_sum(ce);
-  if (l == 0) red[wv][3 * NK] = ce;
+  const float v[1] = {ce};
+  red.put(3 * NK, v);
   __syncthreads();
   const int t = threadIdx.x;
-  if (t < 3 * k1) part[((size_t)b * slabs + s) * k1 * 3 + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
-  else if (t == 3 * NK) cepart[(size_t)b * slabs + s] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+  if (t < 3 * k1) part[((size_t)b * slabs + s) * k1 * 3 + t] = red.sum_f(t);
+  else if (t == 3 * NK) cepart[(size_t)b * slabs + s] = red.sum_f(t);
 }
 
 // ---------------------------------------------------------------- backward
@@ -142,8 +129,8 @@ __global__ __launch_bounds__(256) void ds_loss_fwd_kernel(const float* __restric
 template <int NK>
 __global__ __launch_bounds__(256) void ds_loss_bwd_kernel(const float* __restrict__ z, const long long* __restrict__ labels,
                                                           const float* __restrict__ coef, const float* __restrict__ gout,
-                                                          float* __restrict__ dz, int nb, int h, int w, int factor, int k1, DsGeom g,
-                                                          DsGeom go, int flags, float dice_w, float ce_w, int th, int tw, int tiles_x,
+                                                          float* __restrict__ dz, int nb, int h, int w, int factor, int k1, LossGeom g,
+                                                          LossGeom go, int flags, float dice_w, float ce_w, int th, int tw, int tiles_x,
                                                           int tiles_y) {
   extern __shared__ __attribute__((aligned(16))) float ds_smem[];
   const int tiles = tiles_x * tiles_y;
@@ -196,16 +183,16 @@ __global__ __launch_bounds__(256) void ds_loss_bwd_kernel(const float* __restric
       for (int k = 0; k < NK; ++k)
         if (k < k1) {
           pr[k] *= inv;
-          const float pk = (flags & DS_SOFTMAX) ? pr[k] : v[k];
+          const float pk = (flags & LF_SOFTMAX) ? pr[k] : v[k];
           const float t = (lab == (long long)k) ? 1.f : 0.f;
-          gk[k] = (al[k] * t + be[k] * ((flags & DS_SQUARED) ? 2.f * pk : 1.f)) * dice_w;
+          gk[k] = (al[k] * t + be[k] * ((flags & LF_SQUARED) ? 2.f * pk : 1.f)) * dice_w;
           dot += gk[k] * pr[k];
         }
 #pragma unroll
       for (int k = 0; k < NK; ++k)
         if (k < k1) {
           const float t = (lab == (long long)k) ? 1.f : 0.f;
-          const float dd = (flags & DS_SOFTMAX) ? pr[k] * (gk[k] - dot) : gk[k];
+          const float dd = (flags & LF_SOFTMAX) ? pr[k] * (gk[k] - dot) : gk[k];
           o[k] = go_s * (dd + cew * (tsum * pr[k] - t));
         }
     }
@@ -255,7 +242,7 @@ static void ds_bwd_tile(int factor, int k1, int* th, int* tw) {
 }
 
 static bool ds_shape_ok(int nb, int h, int w, int factor, int k1) {
-  if (nb <= 0 || h <= 0 || w <= 0 || k1 < 1 || k1 > DS_MAXK) return false;
+  if (nb <= 0 || h <= 0 || w <= 0 || k1 < 1 || k1 > LOSS_MAXK) return false;
   if (factor != 2 && factor != 4 && factor != 8 && factor != 16) return false;
   return (int64_t)h * factor * w * factor < ((int64_t)1 << 31);
 }
@@ -271,11 +258,11 @@ extern "C" int mia_ds_loss_fwd(const float* z, const long long* labels, int nb, 
                                float* coef, float* out, int* bad_label, void* stream) {
   MIA_CHECK_ARG(z && labels && workspace && sums && coef && out && bad_label, "mia_ds_loss_fwd: null pointer");
   MIA_CHECK_ARG(ds_shape_ok(nb, h, w, factor, k1), "mia_ds_loss_fwd: nb=%d h=%d w=%d factor=%d k1=%d (factor 2, 4, 8 or 16, k1 in [1,%d])",
-                nb, h, w, factor, k1, DS_MAXK);
+                nb, h, w, factor, k1, LOSS_MAXK);
   MIA_CHECK_ARG(slabs > 0 && (int64_t)nb * slabs < ((int64_t)1 << 31), "mia_ds_loss_fwd: bad slab count");
-  MIA_CHECK_ARG(!(flags & DS_DENSE), "mia_ds_loss_fwd: a dense target is not supported (index labels only)");
+  MIA_CHECK_ARG(!(flags & LF_DENSE), "mia_ds_loss_fwd: a dense target is not supported (index labels only)");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const DsGeom g{sn, sk, sp};
+  const LossGeom g{sn, sk, sp};
   float* part = workspace;
   float* cepart = workspace + (size_t)nb * slabs * k1 * 3;
   const dim3 grid((unsigned)(nb * slabs)), blk(256);
@@ -286,7 +273,7 @@ extern "C" int mia_ds_loss_fwd(const float* z, const long long* labels, int nb, 
                               bad_label);                                                                                                \
   else hipLaunchKernelGGL((ds_loss_fwd_kernel<NK, false>), grid, blk, 0, st, z, labels, h, w, factor, k1, g, flags, slabs, part, cepart,   \
                           bad_label)
-  if (k1 == 2) { DS_FWD(2); } else if (k1 == 3) { DS_FWD(3); } else if (k1 == 4) { DS_FWD(4); } else { DS_FWD(DS_MAXK); }
+  if (k1 == 2) { DS_FWD(2); } else if (k1 == 3) { DS_FWD(3); } else if (k1 == 4) { DS_FWD(4); } else { DS_FWD(LOSS_MAXK); }
 #undef DS_FWD
   MIA_LAUNCH_CHECK();
   return mia_dice_ce_finalize_launch(part, cepart, nb, slabs, k1, (int64_t)h * factor * w * factor, flags, smooth, dice_w, ce_w, sums, coef,
@@ -298,10 +285,10 @@ extern "C" int mia_ds_loss_bwd(const float* z, const long long* labels, const fl
                                int flags, float dice_w, float ce_w, void* stream) {
   MIA_CHECK_ARG(z && labels && coef && dz, "mia_ds_loss_bwd: null pointer");
   MIA_CHECK_ARG(ds_shape_ok(nb, h, w, factor, k1), "mia_ds_loss_bwd: nb=%d h=%d w=%d factor=%d k1=%d (factor 2, 4, 8 or 16, k1 in [1,%d])",
-                nb, h, w, factor, k1, DS_MAXK);
-  MIA_CHECK_ARG(!(flags & DS_DENSE), "mia_ds_loss_bwd: a dense target is not supported (index labels only)");
+                nb, h, w, factor, k1, LOSS_MAXK);
+  MIA_CHECK_ARG(!(flags & LF_DENSE), "mia_ds_loss_bwd: a dense target is not supported (index labels only)");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const DsGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
+  const LossGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
   int th, tw;
   ds_bwd_tile(factor, k1, &th, &tw);
   const int tiles_y = ceil_div(h, th), tiles_x = ceil_div(w, tw);
@@ -311,7 +298,7 @@ extern "C" int mia_ds_loss_bwd(const float* z, const long long* labels, const fl
 #define DS_BWD(NK)                                                                                                                      \
   hipLaunchKernelGGL(ds_loss_bwd_kernel<NK>, grid, blk, lds, st, z, labels, coef, grad_out, dz, nb, h, w, factor, k1, g, go, flags, dice_w, \
                      ce_w, th, tw, tiles_x, tiles_y)
-  if (k1 == 2) { DS_BWD(2); } else if (k1 == 3) { DS_BWD(3); } else if (k1 == 4) { DS_BWD(4); } else { DS_BWD(DS_MAXK); }
+  if (k1 == 2) { DS_BWD(2); } else if (k1 == 3) { DS_BWD(3); } else if (k1 == 4) { DS_BWD(4); } else { DS_BWD(LOSS_MAXK); }
 #undef DS_BWD
   MIA_LAUNCH_CHECK();
   return MIA_OK;

@@ -18,16 +18,14 @@
 // No float atomics, nothing synchronises with the host, every launch goes to the caller's stream.
 #include "common.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)  // ahead of loss_common.h: what this file instantiates from there is compiled without contraction too
+#include "loss_common.h"
 
-#define RL_MAXC 8
 #define RL_DO_BG 1
 #define RL_BATCH 2
 #define RL_IGNORE 4
 #define RL_INDEX 8
 #define RL_TARGET_U8 16
-
-struct RlGeom { int64_t sn, sk, sp; };  // element strides of a logits-shaped tensor: image, channel, pixel
 
 enum { LM_SCALAR = 0, LM_PLANAR4 = 1, LM_CLAST4 = 2 };                      // how a quad of logits is read / written
 enum { TK_DENSE_U8 = 0, TK_DENSE_F32 = 1, TK_INDEX_U8 = 2, TK_INDEX_I64 = 3 };  // target loader
@@ -37,9 +35,7 @@ struct RlTarget {
   const unsigned* bits;   // region_bits[n_labels], index form only
   int n_labels;
   int ct;                 // channels of the dense target: C, or C + 1 with the ignore channel
-  int ign_on;
-  unsigned ign_lo, ign_hi;  // the ignore label as two words (int64 labels)
-  int ign_byte;             // its value when it fits a byte, else -1 (a uint8 label can then never be ignored)
+  LossIgnore ign;
 };
 
 // region bits of one label, or 0 with valid = false (ignored) / bad = true (neither a label of the table nor the ignore label)
@@ -64,13 +60,13 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
 #pragma unroll
         for (int j = 0; j < 4; ++j) t[j][k] = (float)((w >> (8 * j)) & 0xFFu);
       }
-      if (tg.ign_on) ig = *reinterpret_cast<const unsigned*>(base + (int64_t)(tg.ct - 1) * hw);
+      if (tg.ign.on) ig = *reinterpret_cast<const unsigned*>(base + (int64_t)(tg.ct - 1) * hw);
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
 #pragma unroll
         for (int k = 0; k < NC; ++k) t[j][k] = (j < n && k < c) ? (float)base[k * hw + j] : 0.f;
-        if (tg.ign_on && j < n) ig |= (unsigned)base[(int64_t)(tg.ct - 1) * hw + j] << (8 * j);
+        if (tg.ign.on && j < n) ig |= (unsigned)base[(int64_t)(tg.ct - 1) * hw + j] << (8 * j);
       }
     }
 #pragma unroll
@@ -86,7 +82,7 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
 #pragma unroll
         for (int j = 0; j < 4; ++j) t[j][k] = w[j];
       }
-      if (tg.ign_on) {
+      if (tg.ign.on) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(base + (int64_t)(tg.ct - 1) * hw);
 #pragma unroll
         for (int j = 0; j < 4; ++j) ig[j] = w[j];
@@ -96,7 +92,7 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
       for (int j = 0; j < 4; ++j) {
 #pragma unroll
         for (int k = 0; k < NC; ++k) t[j][k] = (j < n && k < c) ? base[k * hw + j] : 0.f;
-        if (tg.ign_on && j < n) ig[j] = base[(int64_t)(tg.ct - 1) * hw + j];
+        if (tg.ign.on && j < n) ig[j] = base[(int64_t)(tg.ct - 1) * hw + j];
       }
     }
 #pragma unroll
@@ -118,9 +114,7 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
     } else {
       const long long* base = static_cast<const long long*>(tg.ptr) + (int64_t)b * hw + 4 * q;
       if (VEC) {
-        const u32x4 l0 = reinterpret_cast<const u32x4*>(base)[0], l1 = reinterpret_cast<const u32x4*>(base)[1];
-        lo[0] = l0[0]; hi[0] = l0[1]; lo[1] = l0[2]; hi[1] = l0[3];
-        lo[2] = l1[0]; hi[2] = l1[1]; lo[3] = l1[2]; hi[3] = l1[3];
+        load_label_quad(base, lo, hi);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -131,7 +125,7 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const bool is_ign = TK == TK_INDEX_U8 ? (int)lo[j] == tg.ign_byte : (tg.ign_on && lo[j] == tg.ign_lo && hi[j] == tg.ign_hi);
+      const bool is_ign = TK == TK_INDEX_U8 ? (int)lo[j] == tg.ign.byte : (tg.ign.on && lo[j] == tg.ign.lo && hi[j] == tg.ign.hi);
       bool v = false, bd = false;
       unsigned bits = 0u;
       if (j < n) bits = rl_label_bits(tg, lo[j], hi[j], is_ign, v, bd);
@@ -145,7 +139,7 @@ __device__ __forceinline__ void rl_load_target(const RlTarget& tg, int b, int64_
 
 // z[j][k] of the pixels 4q + j, j < n, of the image whose logits start at `src`
 template <int NC, int LM>
-__device__ __forceinline__ void rl_load_logits(const float* __restrict__ src, const RlGeom& g, int64_t q, int c, int n, float (&z)[4][NC]) {
+__device__ __forceinline__ void rl_load_logits(const float* __restrict__ src, const LossGeom& g, int64_t q, int c, int n, float (&z)[4][NC]) {
   if (LM == LM_PLANAR4) {
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
@@ -154,17 +148,11 @@ __device__ __forceinline__ void rl_load_logits(const float* __restrict__ src, co
       for (int j = 0; j < 4; ++j) z[j][k] = w[j];
     }
   } else if (LM == LM_CLAST4) {  // four pixels = NC consecutive 16-byte units
-    float flat[4 * NC];
+    f32x4 f[NC];
 #pragma unroll
-    for (int u = 0; u < NC; ++u) {
-      const f32x4 w = *reinterpret_cast<const f32x4*>(src + (4 * q) * NC + 4 * u);
+    for (int u = 0; u < NC; ++u) f[u] = *reinterpret_cast<const f32x4*>(src + (4 * q) * NC + 4 * u);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) flat[4 * u + i] = w[i];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int k = 0; k < NC; ++k) z[j][k] = flat[j * NC + k];
+    for (int j = 0; j < 4; ++j) quad_unpack<NC>(f, j, z[j]);
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -189,12 +177,6 @@ __device__ __forceinline__ RlSig rl_sig(float z) {
   s.sp_pos = fmaxf(z, 0.f) + l;
   s.sp_neg = fmaxf(-z, 0.f) + l;
   return s;
-}
-
-__device__ __forceinline__ int rl_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Per-thread accumulators of the forward pass.  NC is a compile-time bound, c <= NC the live count.
@@ -227,34 +209,28 @@ struct RlAcc {
   }
 };
 
-// Block sums behind ONE barrier (per-wave sums -> LDS -> one thread per value adds the four waves in a fixed order), written to this
-// block's slice of the workspace: [3 c] floats (I, P, G per channel), bce, then [3 c] ints (tp, predicted, labelled), #valid pixels.
+// Block sums behind ONE barrier, written to this block's slice of the workspace: [3 c] floats (I, P, G per channel), bce, then [3 c] ints (tp, predicted, labelled), #valid pixels.
 template <int NC>
 __device__ __forceinline__ void rl_block_store(const RlAcc<NC>& acc, int c, float* __restrict__ slice) {
-  __shared__ float redf[4][3 * NC + 1];
-  __shared__ int redi[4][3 * NC + 1];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  auto red = loss_block_sums<3 * NC + 1, 3 * NC + 1>();
 #pragma unroll
   for (int k = 0; k < NC; ++k)
     if (k < c) {
-      const float a = wave_sum(acc.si[k]), p = wave_sum(acc.sp[k]), g = wave_sum(acc.sg[k]);
-      const int t = rl_wave_sum_i(acc.tp[k]), h = rl_wave_sum_i(acc.pp[k]), m = rl_wave_sum_i(acc.gp[k]);
-      if (l == 0) {
-        redf[w][3 * k] = a; redf[w][3 * k + 1] = p; redf[w][3 * k + 2] = g;
-        redi[w][3 * k] = t; redi[w][3 * k + 1] = h; redi[w][3 * k + 2] = m;
-      }
+      const float fv[3] = {acc.si[k], acc.sp[k], acc.sg[k]};
+      const int iv[3] = {acc.tp[k], acc.pp[k], acc.gp[k]};
+      red.put(3 * k, fv, 3 * k, iv);
     }
-  const float e = wave_sum(acc.bce);
-  const int v = rl_wave_sum_i(acc.nv);
-  if (l == 0) { redf[w][3 * c] = e; redi[w][3 * c] = v; }
+  const float fv[1] = {acc.bce};
+  const int iv[1] = {acc.nv};
+  red.put(3 * c, fv, 3 * c, iv);
   __syncthreads();
   const int nf = 3 * c + 1;
   if ((int)threadIdx.x < nf) {
     const int i = threadIdx.x;
-    slice[i] = ((redf[0][i] + redf[1][i]) + redf[2][i]) + redf[3][i];
+    slice[i] = red.sum_f(i);
   } else if ((int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + nf) {
     const int i = threadIdx.x - 64;
-    reinterpret_cast<int*>(slice + nf)[i] = redi[0][i] + redi[1][i] + redi[2][i] + redi[3][i];
+    reinterpret_cast<int*>(slice + nf)[i] = red.sum_i(i);
   }
 }
 
@@ -267,7 +243,7 @@ __device__ __forceinline__ void rl_load_pw(const float* __restrict__ pw_g, int c
 // ---------------------------------------------------------------- forward: block (b, s) owns the quads [s per, (s + 1) per) of image b
 template <int NC, int LM, int TK>
 __global__ __launch_bounds__(256) void region_loss_fwd_kernel(const float* __restrict__ logits, RlTarget tg, const float* __restrict__ pw_g,
-                                                              int64_t hw, int c, RlGeom g, int slabs, float* __restrict__ ws,
+                                                              int64_t hw, int c, LossGeom g, int slabs, float* __restrict__ ws,
                                                               int* __restrict__ bad_label) {
   const int b = blockIdx.x / slabs, s = blockIdx.x % slabs;
   const int64_t nq = (hw + 3) >> 2, per = (nq + slabs - 1) / slabs, q0 = s * per, q1 = q0 + per < nq ? q0 + per : nq;
@@ -366,16 +342,7 @@ __global__ void region_loss_finalize_kernel(const float* __restrict__ ws, double
     store_data_pad();
     coef[total * 2] = cn;
   }
-  // bad label: the protocol of seg_loss_finalize_kernel -- NaN results, sticky verdict in bad_label[1], working flag re-armed
-  __syncthreads();
-  const int bad = bad_label[0];
-  __syncthreads();
-  if (threadIdx.x == 0) { if (bad) bad_label[1] = 1; bad_label[0] = 0; }
-  if (bad) {
-    const float qn = __builtin_nanf("");
-    if (threadIdx.x < 3) out[threadIdx.x] = qn;
-    for (int i = threadIdx.x; i < total * 2 + 1; i += blockDim.x) coef[i] = qn;
-  }
+  loss_bad_label_verdict(bad_label, out, coef, total * 2 + 1);
 }
 
 // ---------------------------------------------------------------- backward: one pass, a thread owns a quad of one image
@@ -383,7 +350,7 @@ __global__ void region_loss_finalize_kernel(const float* __restrict__ ws, double
 template <int NC, int LM, int TK>
 __global__ __launch_bounds__(256) void region_loss_bwd_kernel(const float* __restrict__ logits, RlTarget tg, const float* __restrict__ pw_g,
                                                               const float* __restrict__ coef, const float* __restrict__ gout,
-                                                              float* __restrict__ dl, int nb, int64_t hw, int c, RlGeom g, RlGeom go) {
+                                                              float* __restrict__ dl, int nb, int64_t hw, int c, LossGeom g, LossGeom go) {
   const int b = blockIdx.y;
   const int64_t nq = (hw + 3) >> 2;
   const float go_s = gout ? gout[0] : 1.f;
@@ -451,11 +418,8 @@ static RlTarget rl_make_target(const void* target, const unsigned* region_bits, 
   t.ptr = target;
   t.bits = region_bits;
   t.n_labels = n_labels;
-  t.ign_on = (flags & RL_IGNORE) ? 1 : 0;
-  t.ct = c + ((flags & RL_INDEX) ? 0 : t.ign_on);
-  t.ign_lo = (unsigned)((uint64_t)ign & 0xFFFFFFFFull);
-  t.ign_hi = (unsigned)((uint64_t)ign >> 32);
-  t.ign_byte = (t.ign_on && ign >= 0 && ign < 256) ? (int)ign : -1;
+  t.ign = make_ignore((flags & RL_IGNORE) != 0, ign);
+  t.ct = c + ((flags & RL_INDEX) ? 0 : t.ign.on);
   return t;
 }
 
@@ -482,7 +446,7 @@ static int rl_check_common(const char* who, const void* logits, const void* targ
                            int64_t hw, int c, int64_t sn, int64_t sk, int64_t sp, int flags) {
   MIA_CHECK_ARG(logits && target, "%s: null pointer", who);
   MIA_CHECK_ARG(nb > 0 && hw > 0 && hw < ((int64_t)1 << 31), "%s: bad shape", who);
-  MIA_CHECK_ARG(c >= 1 && c <= RL_MAXC, "%s: c=%d not in [1,%d]", who, c, RL_MAXC);
+  MIA_CHECK_ARG(c >= 1 && c <= LOSS_MAXK, "%s: c=%d not in [1,%d]", who, c, LOSS_MAXK);
   MIA_CHECK_ARG(c > 1 || (flags & RL_DO_BG), "%s: one channel without MIA_REGLOSS_DO_BG leaves no Dice term", who);
   MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0, "%s: negative strides", who);
   MIA_CHECK_ARG((flags & ~(RL_DO_BG | RL_BATCH | RL_IGNORE | RL_INDEX | RL_TARGET_U8)) == 0, "%s: unknown flag bits in %d", who, flags);
@@ -501,7 +465,7 @@ static int rl_check_common(const char* who, const void* logits, const void* targ
   if (lm == LM_PLANAR4) { RL_LAUNCH_TK(KERNEL, NC, LM_PLANAR4, __VA_ARGS__) }              \
   else { RL_LAUNCH_TK(KERNEL, NC, LM_CLAST4, __VA_ARGS__) }
 #define RL_LAUNCH(KERNEL, ...)                                                             \
-  if (lm == LM_SCALAR) { RL_LAUNCH_TK(KERNEL, RL_MAXC, LM_SCALAR, __VA_ARGS__) }           \
+  if (lm == LM_SCALAR) { RL_LAUNCH_TK(KERNEL, LOSS_MAXK, LM_SCALAR, __VA_ARGS__) }           \
   else if (c == 1) { RL_LAUNCH_LM(KERNEL, 1, __VA_ARGS__) }                                \
   else if (c == 2) { RL_LAUNCH_LM(KERNEL, 2, __VA_ARGS__) }                                \
   else if (c == 3) { RL_LAUNCH_LM(KERNEL, 3, __VA_ARGS__) }                                \
@@ -527,7 +491,7 @@ extern "C" int mia_region_loss_fwd(const float* logits, const void* target, cons
   MIA_CHECK_ARG(slabs > 0 && (int64_t)nb * slabs <= 0x7fffffffLL, "mia_region_loss_fwd: bad slab count %d", slabs);
   MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "mia_region_loss_fwd: workspace must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const RlGeom g{sn, sk, sp};
+  const LossGeom g{sn, sk, sp};
   const RlTarget tg = rl_make_target(target, region_bits, n_labels, c, flags, ignore_label);
   const int tk = rl_target_kind(flags), lm = rl_logits_mode(logits, target, hw, c, sn, sk, sp, flags);
   const dim3 grid((unsigned)(nb * slabs)), blk(256);
@@ -549,7 +513,7 @@ extern "C" int mia_region_loss_bwd(const float* logits, const void* target, cons
   MIA_CHECK_ARG(gsn >= 0 && gsk >= 0 && gsp >= 0, "mia_region_loss_bwd: negative strides");
   MIA_CHECK_ARG(nb <= 65535, "mia_region_loss_bwd: nb=%d images are more than one launch takes", nb);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const RlGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
+  const LossGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
   const RlTarget tg = rl_make_target(target, region_bits, n_labels, c, flags, ignore_label);
   const int tk = rl_target_kind(flags);
   int lm = rl_logits_mode(logits, target, hw, c, sn, sk, sp, flags);

@@ -10,71 +10,47 @@
 // No float atomics anywhere: fp32 partials per block, summed in double in a fixed order by a one-block kernel, so every result is
 // bit-identical run to run.  Counts are integers end to end (G is the integer count of labelled pixels, exact at any size).
 // Nothing here synchronises with the host or sizes an allocation from device data, and every launch goes to the caller's stream.
-// A label that is neither a class nor the ignore label follows the protocol of the fused Dice/CE kernel (head_loss.hip): the pixel
-// is dropped, a working flag is raised, and the finalize kernel turns it into NaN results plus the sticky per-device verdict.
-#include "common.h"
+// A label that is neither a class nor the ignore label follows the protocol of the fused Dice/CE kernel (loss_bad_label_verdict in
+// loss_common.h): the pixel is dropped, a working flag is raised, and the finalize kernel turns it into NaN results plus the sticky
+// per-device verdict.
+#include "loss_common.h"
 
-#define SL_MAXK 8
 #define SL_SOFTMAX 1
 #define SL_DO_BG 2
 #define SL_BATCH 4
 #define SL_LABEL_U8 8
 #define SL_IGNORE 16
 
-struct SlGeom { int64_t sn, sk, sp; };  // element strides of a logits-shaped tensor: image, class, pixel
-
-// Which label values are "ignore": one 64-bit value for int64 labels, one byte (or none) for uint8 labels.
-struct SlIgnore {
-  unsigned lo, hi;  // the ignore label as two words (int64 labels)
-  int on;           // an ignore label is set
-  int byte;         // its value when it fits a byte, else -1 (uint8 labels can then never be ignored)
-};
-
-static SlIgnore make_ignore(int flags, int64_t ign) {
-  SlIgnore g;
-  g.on = (flags & SL_IGNORE) ? 1 : 0;
-  g.lo = (unsigned)((uint64_t)ign & 0xFFFFFFFFull);
-  g.hi = (unsigned)((uint64_t)ign >> 32);
-  g.byte = (g.on && ign >= 0 && ign < 256) ? (int)ign : -1;
-  return g;
-}
-
 // class index in [0, k1), -1 = ignored, -2 = neither (bad label)
-__device__ __forceinline__ int sl_class64(unsigned lo, unsigned hi, int k1, const SlIgnore& g) {
+__device__ __forceinline__ int sl_class64(unsigned lo, unsigned hi, int k1, const LossIgnore& g) {
   if (hi == 0u && lo < (unsigned)k1) return (int)lo;
   return (g.on && lo == g.lo && hi == g.hi) ? -1 : -2;
 }
-__device__ __forceinline__ int sl_class8(unsigned b, int k1, const SlIgnore& g) {
+__device__ __forceinline__ int sl_class8(unsigned b, int k1, const LossIgnore& g) {
   if (b < (unsigned)k1) return (int)b;
   return ((int)b == g.byte) ? -1 : -2;
 }
-__device__ __forceinline__ int sl_class(const long long* labels, int64_t i, int k1, const SlIgnore& g) {
+__device__ __forceinline__ int sl_class(const long long* labels, int64_t i, int k1, const LossIgnore& g) {
   const unsigned long long v = (unsigned long long)labels[i];
   return sl_class64((unsigned)(v & 0xFFFFFFFFull), (unsigned)(v >> 32), k1, g);
 }
-__device__ __forceinline__ int sl_class(const unsigned char* labels, int64_t i, int k1, const SlIgnore& g) {
+__device__ __forceinline__ int sl_class(const unsigned char* labels, int64_t i, int k1, const LossIgnore& g) {
   return sl_class8(labels[i], k1, g);
 }
 
 // four consecutive labels of one thread's pixel quad (quad index q of the image whose labels start at `lb`)
 template <int K1>
-__device__ __forceinline__ void sl_quad_classes(const long long* lb, size_t q, const SlIgnore& g, int (&c)[4]) {
-  const u32x4* p = reinterpret_cast<const u32x4*>(lb);
-  const u32x4 l0 = p[2 * q], l1 = p[2 * q + 1];
-  c[0] = sl_class64(l0[0], l0[1], K1, g); c[1] = sl_class64(l0[2], l0[3], K1, g);
-  c[2] = sl_class64(l1[0], l1[1], K1, g); c[3] = sl_class64(l1[2], l1[3], K1, g);
+__device__ __forceinline__ void sl_quad_classes(const long long* lb, size_t q, const LossIgnore& g, int (&c)[4]) {
+  unsigned lo[4], hi[4];
+  load_label_quad(lb + 4 * q, lo, hi);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c[j] = sl_class64(lo[j], hi[j], K1, g);
 }
 template <int K1>
-__device__ __forceinline__ void sl_quad_classes(const unsigned char* lb, size_t q, const SlIgnore& g, int (&c)[4]) {
+__device__ __forceinline__ void sl_quad_classes(const unsigned char* lb, size_t q, const LossIgnore& g, int (&c)[4]) {
   const unsigned w = reinterpret_cast<const unsigned*>(lb)[q];
 #pragma unroll
   for (int j = 0; j < 4; ++j) c[j] = sl_class8((w >> (8 * j)) & 0xFFu, K1, g);
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Per-thread accumulators of the forward pass.  NK is a compile-time bound, k1 <= NK the live count.
@@ -120,30 +96,27 @@ struct SlAcc {
   }
 };
 
-// Block sums of all accumulators behind ONE barrier (per-wave sums -> LDS -> one thread per value adds the four waves), written to
-// this block's slice of the workspace: [2 k1] floats (I, P per class), cen, ced, then [3 k1] ints (tp, labelled, predicted).
+// Block sums of all accumulators behind ONE barrier, written to this block's slice of the workspace: [2 k1] floats (I, P per class), cen, ced, then [3 k1] ints (tp, labelled, predicted).
 template <int NK>
 __device__ __forceinline__ void sl_block_store(const SlAcc<NK>& acc, int k1, float* __restrict__ slice) {
-  __shared__ float redf[4][2 * NK + 2];
-  __shared__ int redi[4][3 * NK];
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  auto red = loss_block_sums<2 * NK + 2, 3 * NK>();
 #pragma unroll
   for (int k = 0; k < NK; ++k)
     if (k < k1) {
-      const float a = wave_sum(acc.si[k]), c = wave_sum(acc.sp[k]);
-      const int t = wave_sum_i(acc.tp[k]), g = wave_sum_i(acc.cl[k]), h = wave_sum_i(acc.ca[k]);
-      if (l == 0) { redf[w][2 * k] = a; redf[w][2 * k + 1] = c; redi[w][3 * k] = t; redi[w][3 * k + 1] = g; redi[w][3 * k + 2] = h; }
+      const float fv[2] = {acc.si[k], acc.sp[k]};
+      const int iv[3] = {acc.tp[k], acc.cl[k], acc.ca[k]};
+      red.put(2 * k, fv, 3 * k, iv);
     }
-  const float n = wave_sum(acc.cen), d = wave_sum(acc.ced);
-  if (l == 0) { redf[w][2 * k1] = n; redf[w][2 * k1 + 1] = d; }
+  const float ce[2] = {acc.cen, acc.ced};
+  red.put(2 * k1, ce);
   __syncthreads();
   const int nf = 2 * k1 + 2, ni = 3 * k1;
   if ((int)threadIdx.x < nf) {
     const int i = threadIdx.x;
-    slice[i] = redf[0][i] + redf[1][i] + redf[2][i] + redf[3][i];
+    slice[i] = red.sum_f(i);
   } else if ((int)threadIdx.x >= 64 && (int)threadIdx.x < 64 + ni) {
     const int i = threadIdx.x - 64;
-    reinterpret_cast<int*>(slice + nf)[i] = redi[0][i] + redi[1][i] + redi[2][i] + redi[3][i];
+    reinterpret_cast<int*>(slice + nf)[i] = red.sum_i(i);
   }
 }
 
@@ -156,26 +129,26 @@ __device__ __forceinline__ void sl_load_weights(const float* __restrict__ cw_g, 
 // ---------------------------------------------------------------- forward, any strides / k1 <= 8 / ragged size
 template <typename LT>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
-                                                           const float* __restrict__ cw_g, int64_t hw, int k1, SlGeom g, int flags,
-                                                           SlIgnore ign, int slabs, float* __restrict__ ws, int* __restrict__ bad_label) {
+                                                           const float* __restrict__ cw_g, int64_t hw, int k1, LossGeom g, int flags,
+                                                           LossIgnore ign, int slabs, float* __restrict__ ws, int* __restrict__ bad_label) {
   const int b = blockIdx.x / slabs, s = blockIdx.x % slabs;
   const int64_t per = (hw + slabs - 1) / slabs, r0 = s * per, r1 = r0 + per < hw ? r0 + per : hw;
-  float cw[SL_MAXK];
-  sl_load_weights<SL_MAXK>(cw_g, k1, cw);
-  SlAcc<SL_MAXK> acc;
+  float cw[LOSS_MAXK];
+  sl_load_weights<LOSS_MAXK>(cw_g, k1, cw);
+  SlAcc<LOSS_MAXK> acc;
   acc.clear();
   const float* base = logits + b * g.sn;
   bool bad = false;
   for (int64_t p = r0 + threadIdx.x; p < r1; p += 256) {
-    float v[SL_MAXK];
+    float v[LOSS_MAXK];
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k) v[k] = (k < k1) ? base[p * g.sp + k * g.sk] : 0.f;
+    for (int k = 0; k < LOSS_MAXK; ++k) v[k] = (k < k1) ? base[p * g.sp + k * g.sk] : 0.f;
     const int c = sl_class(labels, (int64_t)b * hw + p, k1, ign);
     bad |= c == -2;
     acc.pixel(v, k1, c, (flags & SL_SOFTMAX) != 0, cw);
   }
   if (bad) *bad_label = 1;
-  sl_block_store<SL_MAXK>(acc, k1, ws + (size_t)blockIdx.x * (5 * k1 + 2));
+  sl_block_store<LOSS_MAXK>(acc, k1, ws + (size_t)blockIdx.x * (5 * k1 + 2));
 }
 
 // ---------------------------------------------------------------- forward, fast path
@@ -183,7 +156,7 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(const float* __restri
 // step: K1 16-byte loads of logits and the four labels in two 16-byte loads (int64) or one 4-byte load (uint8), two steps in flight.
 template <int K1, typename LT>
 __global__ __launch_bounds__(256) void seg_loss_fwd_fast_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
-                                                                const float* __restrict__ cw_g, int hw, int flags, SlIgnore ign,
+                                                                const float* __restrict__ cw_g, int hw, int flags, LossIgnore ign,
                                                                 int slabs, float* __restrict__ ws, int* __restrict__ bad_label) {
   const int b = blockIdx.x / slabs, s = blockIdx.x % slabs;
   const int quads = hw >> 2;
@@ -200,8 +173,7 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_fast_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float v[K1];
-#pragma unroll
-      for (int k = 0; k < K1; ++k) v[k] = f[(j * K1 + k) >> 2][(j * K1 + k) & 3];
+      quad_unpack<K1>(f, j, v);
       bad |= c[j] == -2;
       acc.pixel(v, K1, c[j], softmax, cw);
     }
@@ -292,16 +264,7 @@ __global__ void seg_loss_finalize_kernel(const float* __restrict__ ws, double* _
     out[0] = (float)((double)ce_w * c + (double)dice_w * d);
     coef[total * 2] = any ? (float)((double)ce_w / w) : 0.f;
   }
-  // bad label: same protocol as dice_ce_finalize_kernel (head_loss.hip) -- NaN results, sticky verdict in bad_label[1], working flag re-armed
-  __syncthreads();
-  const int bad = bad_label[0];
-  __syncthreads();
-  if (threadIdx.x == 0) { if (bad) bad_label[1] = 1; bad_label[0] = 0; }
-  if (bad) {
-    const float qn = __builtin_nanf("");
-    if (threadIdx.x < 3) out[threadIdx.x] = qn;
-    for (int i = threadIdx.x; i < total * 2 + 1; i += blockDim.x) coef[i] = qn;
-  }
+  loss_bad_label_verdict(bad_label, out, coef, total * 2 + 1);
 }
 
 // ---------------------------------------------------------------- backward
@@ -340,28 +303,28 @@ template <typename LT>
 __global__ __launch_bounds__(256) void seg_loss_bwd_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
                                                            const float* __restrict__ cw_g, const float* __restrict__ coef,
                                                            const float* __restrict__ gout, float* __restrict__ dl, int nb, int64_t hw,
-                                                           int k1, SlGeom g, SlGeom go, int flags, SlIgnore ign) {
+                                                           int k1, LossGeom g, LossGeom go, int flags, LossIgnore ign) {
   const int64_t total = (int64_t)nb * hw;
   const float go_s = gout ? gout[0] : 1.f;
   const float cecoef = go_s * coef[(size_t)nb * k1 * 2];
-  float cw[SL_MAXK];
-  sl_load_weights<SL_MAXK>(cw_g, k1, cw);
+  float cw[LOSS_MAXK];
+  sl_load_weights<LOSS_MAXK>(cw_g, k1, cw);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int b = (int)(i / hw);
     const int64_t p = i - (int64_t)b * hw;
     const float* src = logits + b * g.sn + p * g.sp;
-    float v[SL_MAXK], al[SL_MAXK], be[SL_MAXK], o[SL_MAXK];
+    float v[LOSS_MAXK], al[LOSS_MAXK], be[LOSS_MAXK], o[LOSS_MAXK];
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k) {
+    for (int k = 0; k < LOSS_MAXK; ++k) {
       v[k] = (k < k1) ? src[k * g.sk] : 0.f;
       al[k] = (k < k1) ? go_s * coef[((size_t)b * k1 + k) * 2] : 0.f;
       be[k] = (k < k1) ? go_s * coef[((size_t)b * k1 + k) * 2 + 1] : 0.f;
     }
     const int c = sl_class(labels, i, k1, ign);
-    sl_pixel_bwd<SL_MAXK>(v, k1, c, (flags & SL_SOFTMAX) != 0, cw, al, be, cecoef, o);
+    sl_pixel_bwd<LOSS_MAXK>(v, k1, c, (flags & SL_SOFTMAX) != 0, cw, al, be, cecoef, o);
     float* dst = dl + b * go.sn + p * go.sp;
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k)
+    for (int k = 0; k < LOSS_MAXK; ++k)
       if (k < k1) dst[k * go.sk] = o[k];
   }
 }
@@ -370,7 +333,7 @@ template <int K1, typename LT>
 __global__ __launch_bounds__(256) void seg_loss_bwd_fast_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
                                                                 const float* __restrict__ cw_g, const float* __restrict__ coef,
                                                                 const float* __restrict__ gout, float* __restrict__ dl, int nb, int hw,
-                                                                int flags, SlIgnore ign) {
+                                                                int flags, LossIgnore ign) {
   const int b = blockIdx.y;
   const int quads = hw >> 2;
   const float go_s = gout ? gout[0] : 1.f;
@@ -424,14 +387,14 @@ static size_t sl_slices_words(int nb, int k1, int slabs) {
 #define TK_SUM_BLOCKS 256
 #define TK_HIST_WORDS (4 * 256)
 
-__device__ __forceinline__ float tk_pixel_nll(const float (&v)[SL_MAXK], int k1, int c, const float (&cw)[SL_MAXK]) {
+__device__ __forceinline__ float tk_pixel_nll(const float (&v)[LOSS_MAXK], int k1, int c, const float (&cw)[LOSS_MAXK]) {
   float mx = v[0];
 #pragma unroll
-  for (int k = 1; k < SL_MAXK; ++k)
+  for (int k = 1; k < LOSS_MAXK; ++k)
     if (k < k1) mx = fmaxf(mx, v[k]);
   float se = 0.f, vc = 0.f, wc = 0.f;
 #pragma unroll
-  for (int k = 0; k < SL_MAXK; ++k)
+  for (int k = 0; k < LOSS_MAXK; ++k)
     if (k < k1) { se += expf(v[k] - mx); vc = (c == k) ? v[k] : vc; wc = (c == k) ? cw[k] : wc; }
   const float r = wc * ((mx + logf(se)) - vc);
   return c >= 0 ? (r < 0.f ? 0.f : r) : 0.f;  // a negative zero would order above every positive value
@@ -439,8 +402,8 @@ __device__ __forceinline__ float tk_pixel_nll(const float (&v)[SL_MAXK], int k1,
 
 template <typename LT>
 __global__ __launch_bounds__(256) void topk_nll_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
-                                                       const float* __restrict__ cw_g, int nb, int64_t hw, int k1, SlGeom g,
-                                                       SlIgnore ign, unsigned n_top, float* __restrict__ nll,
+                                                       const float* __restrict__ cw_g, int nb, int64_t hw, int k1, LossGeom g,
+                                                       LossIgnore ign, unsigned n_top, float* __restrict__ nll,
                                                        unsigned* __restrict__ hist, unsigned* __restrict__ state,
                                                        int* __restrict__ bad_label) {
   if (blockIdx.x == 0) {  // the select's scratch is reset here: later kernels on the stream are the only readers
@@ -448,16 +411,16 @@ __global__ __launch_bounds__(256) void topk_nll_kernel(const float* __restrict__
     if (threadIdx.x == 0) { state[0] = 0u; state[1] = n_top; state[2] = 0u; }
   }
   const int64_t total = (int64_t)nb * hw;
-  float cw[SL_MAXK];
-  sl_load_weights<SL_MAXK>(cw_g, k1, cw);
+  float cw[LOSS_MAXK];
+  sl_load_weights<LOSS_MAXK>(cw_g, k1, cw);
   bool bad = false;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int b = (int)(i / hw);
     const int64_t p = i - (int64_t)b * hw;
     const float* src = logits + b * g.sn + p * g.sp;
-    float v[SL_MAXK];
+    float v[LOSS_MAXK];
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k) v[k] = (k < k1) ? src[k * g.sk] : 0.f;
+    for (int k = 0; k < LOSS_MAXK; ++k) v[k] = (k < k1) ? src[k * g.sk] : 0.f;
     const int c = sl_class(labels, i, k1, ign);
     bad |= c == -2;
     nll[i] = tk_pixel_nll(v, k1, c, cw);
@@ -548,15 +511,15 @@ template <typename LT>
 __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__ logits, const LT* __restrict__ labels,
                                                        const float* __restrict__ cw_g, const float* __restrict__ nll,
                                                        const float* __restrict__ sel, const float* __restrict__ gout,
-                                                       float* __restrict__ dl, int nb, int64_t hw, int k1, SlGeom g, SlGeom go,
-                                                       SlIgnore ign) {
+                                                       float* __restrict__ dl, int nb, int64_t hw, int k1, LossGeom g, LossGeom go,
+                                                       LossIgnore ign) {
   const int64_t total = (int64_t)nb * hw;
   const float go_s = gout ? gout[0] : 1.f;
   const unsigned tau = __builtin_bit_cast(unsigned, sel[0]);
   const float sgt = go_s * sel[1], seq = go_s * sel[2];
   const unsigned* bits = reinterpret_cast<const unsigned*>(nll);
-  float cw[SL_MAXK];
-  sl_load_weights<SL_MAXK>(cw_g, k1, cw);
+  float cw[LOSS_MAXK];
+  sl_load_weights<LOSS_MAXK>(cw_g, k1, cw);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int b = (int)(i / hw);
     const int64_t p = i - (int64_t)b * hw;
@@ -564,28 +527,28 @@ __global__ __launch_bounds__(256) void topk_bwd_kernel(const float* __restrict__
     const int c = sl_class(labels, i, k1, ign);
     const bool live = c >= 0 && u >= tau;
     float* dst = dl + b * go.sn + p * go.sp;
-    float o[SL_MAXK];
+    float o[LOSS_MAXK];
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k) o[k] = 0.f;
+    for (int k = 0; k < LOSS_MAXK; ++k) o[k] = 0.f;
     if (live) {
       const float* src = logits + b * g.sn + p * g.sp;
-      float v[SL_MAXK], pr[SL_MAXK], mx, se = 0.f, wc = 0.f;
+      float v[LOSS_MAXK], pr[LOSS_MAXK], mx, se = 0.f, wc = 0.f;
 #pragma unroll
-      for (int k = 0; k < SL_MAXK; ++k) v[k] = (k < k1) ? src[k * g.sk] : 0.f;
+      for (int k = 0; k < LOSS_MAXK; ++k) v[k] = (k < k1) ? src[k * g.sk] : 0.f;
       mx = v[0];
 #pragma unroll
-      for (int k = 1; k < SL_MAXK; ++k)
+      for (int k = 1; k < LOSS_MAXK; ++k)
         if (k < k1) mx = fmaxf(mx, v[k]);
 #pragma unroll
-      for (int k = 0; k < SL_MAXK; ++k)
+      for (int k = 0; k < LOSS_MAXK; ++k)
         if (k < k1) { pr[k] = expf(v[k] - mx); se += pr[k]; wc = (c == k) ? cw[k] : wc; }
       const float sc = (u > tau ? sgt : seq) * wc, inv = 1.f / se;
 #pragma unroll
-      for (int k = 0; k < SL_MAXK; ++k)
+      for (int k = 0; k < LOSS_MAXK; ++k)
         if (k < k1) o[k] = sc * (pr[k] * inv - (c == k ? 1.f : 0.f));
     }
 #pragma unroll
-    for (int k = 0; k < SL_MAXK; ++k)
+    for (int k = 0; k < LOSS_MAXK; ++k)
       if (k < k1) dst[k * go.sk] = o[k];
   }
 }
@@ -606,11 +569,11 @@ extern "C" int mia_seg_loss_fwd(const float* logits, const void* labels, const f
                                 int slabs, float* workspace, float* coef, float* out, int64_t* counts, int* bad_label, void* stream) {
   MIA_CHECK_ARG(logits && labels && workspace && coef && out && counts && bad_label, "mia_seg_loss_fwd: null pointer");
   MIA_CHECK_ARG(nb > 0 && hw > 0 && slabs > 0, "mia_seg_loss_fwd: bad shape");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= SL_MAXK, "mia_seg_loss_fwd: k1=%d not in [1,%d]", k1, SL_MAXK);
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_seg_loss_fwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
   MIA_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "mia_seg_loss_fwd: workspace must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SlGeom g{sn, sk, sp};
-  const SlIgnore ign = make_ignore(flags, ignore_label);
+  const LossGeom g{sn, sk, sp};
+  const LossIgnore ign = make_ignore((flags & SL_IGNORE) != 0, ignore_label);
   const bool u8 = (flags & SL_LABEL_U8) != 0;
   const dim3 grid((unsigned)(nb * slabs)), blk(256);
   const long long* l64 = static_cast<const long long*>(labels);
@@ -639,10 +602,10 @@ extern "C" int mia_seg_loss_bwd(const float* logits, const void* labels, const f
                                 float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t gsn, int64_t gsk,
                                 int64_t gsp, int flags, int64_t ignore_label, void* stream) {
   MIA_CHECK_ARG(logits && labels && coef && dlogits && nb > 0 && hw > 0, "mia_seg_loss_bwd: bad arguments");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= SL_MAXK, "mia_seg_loss_bwd: k1=%d not in [1,%d]", k1, SL_MAXK);
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_seg_loss_bwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SlGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
-  const SlIgnore ign = make_ignore(flags, ignore_label);
+  const LossGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
+  const LossIgnore ign = make_ignore((flags & SL_IGNORE) != 0, ignore_label);
   const bool u8 = (flags & SL_LABEL_U8) != 0;
   const long long* l64 = static_cast<const long long*>(labels);
   const unsigned char* l8 = static_cast<const unsigned char*>(labels);
@@ -678,13 +641,13 @@ extern "C" int mia_topk_ce_fwd(const float* logits, const void* labels, const fl
                                int* bad_label, void* stream) {
   MIA_CHECK_ARG(logits && labels && workspace && out && bad_label, "mia_topk_ce_fwd: null pointer");
   MIA_CHECK_ARG(nb > 0 && hw > 0, "mia_topk_ce_fwd: bad shape");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= SL_MAXK, "mia_topk_ce_fwd: k1=%d not in [1,%d]", k1, SL_MAXK);
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_topk_ce_fwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
   const int64_t total = (int64_t)nb * hw;
   MIA_CHECK_ARG(total < ((int64_t)1 << 31), "mia_topk_ce_fwd: more than 2^31 pixels");
   MIA_CHECK_ARG(n_top >= 0 && n_top <= total, "mia_topk_ce_fwd: n_top=%lld not in [0, %lld]", (long long)n_top, (long long)total);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SlGeom g{sn, sk, sp};
-  const SlIgnore ign = make_ignore(flags, ignore_label);
+  const LossGeom g{sn, sk, sp};
+  const LossIgnore ign = make_ignore((flags & SL_IGNORE) != 0, ignore_label);
   float* nll = workspace;
   float* sel = workspace + total;
   unsigned* hist = reinterpret_cast<unsigned*>(sel + 4);
@@ -711,10 +674,10 @@ extern "C" int mia_topk_ce_bwd(const float* logits, const void* labels, const fl
                                const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
                                int64_t gsn, int64_t gsk, int64_t gsp, int flags, int64_t ignore_label, void* stream) {
   MIA_CHECK_ARG(logits && labels && workspace && dlogits && nb > 0 && hw > 0, "mia_topk_ce_bwd: bad arguments");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= SL_MAXK, "mia_topk_ce_bwd: k1=%d not in [1,%d]", k1, SL_MAXK);
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_topk_ce_bwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SlGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
-  const SlIgnore ign = make_ignore(flags, ignore_label);
+  const LossGeom g{sn, sk, sp}, go{gsn, gsk, gsp};
+  const LossIgnore ign = make_ignore((flags & SL_IGNORE) != 0, ignore_label);
   const int64_t total = (int64_t)nb * hw;
   const float* nll = workspace;
   const float* sel = workspace + total;

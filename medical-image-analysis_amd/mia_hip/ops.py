@@ -1163,16 +1163,47 @@ def loss_flags(softmax: bool, do_bg: bool, batch: bool, squared: bool) -> int:
 
 
 _BAD_FLAGS = {}
+_LAST_BAD_LABEL = None  # the flags of the latest loss forward: ONE sticky verdict per device, read by check_labels()
 
 
 def _bad_flags(dev) -> torch.Tensor:
-    """Per-device int32[2], zeroed once: allocating and clearing a flag per loss call would put two fill kernels in every step."""
+    """Per-device int32[2], zeroed once: allocating and clearing a flag per loss call would put two fill kernels in every step.
+    [0] working flag (set by the pixel kernels, re-armed by finalize), [1] sticky verdict.  Every loss forward takes its flags
+    here, which also makes them the ones check_labels() looks at."""
+    global _LAST_BAD_LABEL
     key = (dev.type, dev.index)
     t = _BAD_FLAGS.get(key)
     if t is None:
         t = torch.zeros(2, device=dev, dtype=torch.int32)
         _BAD_FLAGS[key] = t
+    _LAST_BAD_LABEL = DiceCEFn.last_bad_label = t  # the class attribute is the holder's older name, kept readable
     return t
+
+
+def _loss_logits(logits: torch.Tensor):
+    """fp32 logits whose pixel dims collapse (made contiguous otherwise) and their (sn, sk, sp) strides."""
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    st = _pix_strides(logits)
+    if st is None:
+        logits = logits.contiguous()
+        st = _pix_strides(logits)
+    return logits, st
+
+
+def _loss_slabs(hw: int) -> int:
+    """Blocks per image of a loss forward: one per 8192 pixels, at most 256."""
+    return max(1, min(256, hw // 8192))
+
+
+def _loss_bwd_begin(logits: torch.Tensor, gout: torch.Tensor):
+    """(dl, gst, g): the logits gradient to fill (it keeps the logits' dense strides), its strides, grad_out as one fp32 value."""
+    dl = torch.empty_like(logits)
+    return dl, _pix_strides(dl), gout.reshape(1).float().contiguous()
+
+
+def _strides_i64(st):
+    return _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2])
 
 
 class DiceCEFn(torch.autograd.Function):
@@ -1182,12 +1213,7 @@ class DiceCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, flags: int, smooth: float, dice_w: float, ce_w: float, which: int):
         _need_dev(logits, labels)
-        if logits.dtype != torch.float32:
-            logits = logits.float()
-        st = _pix_strides(logits)
-        if st is None:
-            logits = logits.contiguous()
-            st = _pix_strides(logits)
+        logits, st = _loss_logits(logits)
         b, k1, h, w = logits.shape
         if labels.shape == logits.shape and k1 > 1:
             # dense (already one-hot / soft) target: the reference skips its encoder (dice_loss.py:40-41) and
@@ -1200,19 +1226,18 @@ class DiceCEFn(torch.autograd.Function):
                 labels = labels.long()
             labels = labels.contiguous()
         hw = h * w
-        slabs = max(1, min(256, hw // 8192))
+        slabs = _loss_slabs(hw)
         dev = logits.device
         ws = torch.empty(lib().mia_dice_ce_workspace(b, k1, slabs), device=dev, dtype=torch.float32)
         sums = torch.empty((b, k1, 3), device=dev, dtype=torch.float32)
         coef = torch.empty((b, k1, 2), device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
         out = torch.empty(3, device=dev, dtype=torch.float32)
-        bad = _bad_flags(dev)  # [0] working flag (set by the pixel kernels, re-armed by finalize), [1] verdict of the latest forward
-        call("mia_dice_ce_fwd", _p(logits), _p(labels), b, _c_i64(hw), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), flags,
+        bad = _bad_flags(dev)
+        call("mia_dice_ce_fwd", _p(logits), _p(labels), b, _c_i64(hw), k1, *_strides_i64(st), flags,
              _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(sums), _p(coef), _p(out), _p(bad), _stream())
         ctx.save_for_backward(logits, labels, coef)
         ctx.flags, ctx.dice_w, ctx.ce_w, ctx.st = flags, dice_w, ce_w, st
         ctx.bad = bad
-        DiceCEFn.last_bad_label = bad
         DiceCEFn.last_sums = sums
         return out[which]
 
@@ -1220,13 +1245,10 @@ class DiceCEFn(torch.autograd.Function):
     def backward(ctx, gout):
         logits, labels, coef = ctx.saved_tensors
         b, k1, h, w = logits.shape
-        dl = torch.empty_like(logits)  # preserves (dense) strides
-        gst = _pix_strides(dl)
-        g = gout.reshape(1).float().contiguous()
+        dl, gst, g = _loss_bwd_begin(logits, gout)
         st = ctx.st
-        call("mia_dice_ce_bwd", _p(logits), _p(labels), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1, _c_i64(st[0]),
-             _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_float(ctx.dice_w),
-             _c_float(ctx.ce_w), _stream())
+        call("mia_dice_ce_bwd", _p(logits), _p(labels), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1, *_strides_i64(st),
+             *_strides_i64(gst), ctx.flags, _c_float(ctx.dice_w), _c_float(ctx.ce_w), _stream())
         return dl, None, None, None, None, None, None
 
 
@@ -1242,7 +1264,7 @@ def check_labels() -> None:
     forward in between (validation, a second loss term) does not erase it; this call reads it and clears it.
     Ordering contract: every loss forward whose labels you want checked must have been ISSUED on the current stream before
     this call; losses running on other streams of the same device share the flag (their verdicts OR together)."""
-    bad = DiceCEFn.last_bad_label
+    bad = _LAST_BAD_LABEL  # set by _bad_flags() in every loss forward; assigning DiceCEFn.last_bad_label yourself has no effect here
     if bad is not None and int(bad[1].item()) != 0:
         bad[1].zero_()
         raise MiaError("Dice/CE loss: a label lies outside [0, num_classes] (e.g. 255-valued masks or ignore_index -100); "
@@ -1261,12 +1283,7 @@ class UpsampleDiceCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, labels, factor: int, flags: int, smooth: float, dice_w: float, ce_w: float, which: int):
         _need_dev(z, labels)
-        if z.dtype != torch.float32:
-            z = z.float()
-        st = _pix_strides(z)
-        if st is None:
-            z = z.contiguous()
-            st = _pix_strides(z)
+        z, st = _loss_logits(z)
         b, k1, h, w = z.shape
         factor = int(factor)
         if factor not in DS_LOSS_FACTORS or not 1 <= k1 <= DS_LOSS_MAX_CLASSES:
@@ -1279,18 +1296,17 @@ class UpsampleDiceCEFn(torch.autograd.Function):
             labels = labels.long()
         labels = labels.contiguous()
         hw = h * factor * w * factor
-        slabs = max(1, min(256, hw // 8192))
+        slabs = _loss_slabs(hw)
         dev = z.device
         ws = torch.empty(lib().mia_ds_loss_workspace(b, k1, slabs), device=dev, dtype=torch.float32)
         sums = torch.empty((b, k1, 3), device=dev, dtype=torch.float32)
         coef = torch.empty((b, k1, 2), device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
         out = torch.empty(3, device=dev, dtype=torch.float32)
         bad = _bad_flags(dev)
-        call("mia_ds_loss_fwd", _p(z), _p(labels), b, h, w, factor, k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), flags,
+        call("mia_ds_loss_fwd", _p(z), _p(labels), b, h, w, factor, k1, *_strides_i64(st), flags,
              _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(sums), _p(coef), _p(out), _p(bad), _stream())
         ctx.save_for_backward(z, labels, coef)
         ctx.factor, ctx.flags, ctx.dice_w, ctx.ce_w, ctx.st = factor, flags, dice_w, ce_w, st
-        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
         DiceCEFn.last_sums = sums
         return out[which]
 
@@ -1298,13 +1314,10 @@ class UpsampleDiceCEFn(torch.autograd.Function):
     def backward(ctx, gout):
         z, labels, coef = ctx.saved_tensors
         b, k1, h, w = z.shape
-        dz = torch.empty_like(z)  # preserves (dense) strides
-        gst = _pix_strides(dz)
-        g = gout.reshape(1).float().contiguous()
+        dz, gst, g = _loss_bwd_begin(z, gout)
         st = ctx.st
-        call("mia_ds_loss_bwd", _p(z), _p(labels), _p(coef), _p(g), _p(dz), b, h, w, ctx.factor, k1, _c_i64(st[0]), _c_i64(st[1]),
-             _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_float(ctx.dice_w), _c_float(ctx.ce_w),
-             _stream())
+        call("mia_ds_loss_bwd", _p(z), _p(labels), _p(coef), _p(g), _p(dz), b, h, w, ctx.factor, k1, *_strides_i64(st),
+             *_strides_i64(gst), ctx.flags, _c_float(ctx.dice_w), _c_float(ctx.ce_w), _stream())
         return dz, None, None, None, None, None, None, None
 
 
@@ -1319,12 +1332,7 @@ def _seg_loss_inputs(logits, labels, class_w, flags: int, ignore_label):
     _need_dev(logits, labels, class_w)
     if logits.ndim != 4:
         raise NotImplementedError("the HIP segmentation losses implement 2-D inputs [B, K, H, W]")
-    if logits.dtype != torch.float32:
-        logits = logits.float()
-    st = _pix_strides(logits)
-    if st is None:
-        logits = logits.contiguous()
-        st = _pix_strides(logits)
+    logits, st = _loss_logits(logits)
     b, k1, h, w = logits.shape
     if labels.numel() != b * h * w:
         raise MiaError(f"labels {tuple(labels.shape)} do not index the pixels of logits {tuple(logits.shape)}")
@@ -1355,20 +1363,19 @@ class SegLossFn(torch.autograd.Function):
         logits, labels, class_w, st, flags, ign = _seg_loss_inputs(logits, labels, class_w, flags, ignore_label)
         b, k1, h, w = logits.shape
         hw = h * w
-        slabs = max(1, min(256, hw // 8192))
+        slabs = _loss_slabs(hw)
         dev = logits.device
         ws = torch.empty((lib().mia_seg_loss_workspace(b, k1, slabs) + 1) // 2, device=dev, dtype=torch.float64)  # 8-byte aligned
         coef = torch.empty(b * k1 * 2 + 1, device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
         out = torch.empty(3, device=dev, dtype=torch.float32)
         counts = torch.empty((b, k1, 3), device=dev, dtype=torch.int64)
         bad = _bad_flags(dev)
-        call("mia_seg_loss_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(hw), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]),
+        call("mia_seg_loss_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(hw), k1, *_strides_i64(st),
              flags, _c_i64(ign), _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(coef), _p(out), _p(counts),
              _p(bad), _stream())
         ctx.save_for_backward(logits, labels, coef)
         ctx.class_w = class_w
         ctx.flags, ctx.ign, ctx.st = flags, ign, st
-        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
         SegLossFn.last_out = out
         SegLossFn.last_counts = counts
         return out[which]
@@ -1377,12 +1384,10 @@ class SegLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         logits, labels, coef = ctx.saved_tensors
         b, k1, h, w = logits.shape
-        dl = torch.empty_like(logits)  # preserves (dense) strides
-        gst = _pix_strides(dl)
-        g = gout.reshape(1).float().contiguous()
+        dl, gst, g = _loss_bwd_begin(logits, gout)
         st = ctx.st
         call("mia_seg_loss_bwd", _p(logits), _p(labels), _p(ctx.class_w), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1,
-             _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_i64(ctx.ign),
+             *_strides_i64(st), *_strides_i64(gst), ctx.flags, _c_i64(ctx.ign),
              _stream())
         return dl, None, None, None, None, None, None, None, None
 
@@ -1411,12 +1416,11 @@ class TopKCEFn(torch.autograd.Function):
         ws = torch.empty(words, device=dev, dtype=torch.float32)
         out = torch.empty(1, device=dev, dtype=torch.float32)
         bad = _bad_flags(dev)
-        call("mia_topk_ce_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(h * w), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]),
+        call("mia_topk_ce_fwd", _p(logits), _p(labels), _p(class_w), b, _c_i64(h * w), k1, *_strides_i64(st),
              flags, _c_i64(ign), _c_i64(n_top), _p(ws), _p(out), _p(bad), _stream())
         ctx.save_for_backward(logits, labels, ws)
         ctx.class_w = class_w
         ctx.flags, ctx.ign, ctx.st = flags, ign, st
-        DiceCEFn.last_bad_label = bad
         TopKCEFn.last_threshold = ws[n_pix]
         return out[0]
 
@@ -1424,12 +1428,10 @@ class TopKCEFn(torch.autograd.Function):
     def backward(ctx, gout):
         logits, labels, ws = ctx.saved_tensors
         b, k1, h, w = logits.shape
-        dl = torch.empty_like(logits)
-        gst = _pix_strides(dl)
-        g = gout.reshape(1).float().contiguous()
+        dl, gst, g = _loss_bwd_begin(logits, gout)
         st = ctx.st
-        call("mia_topk_ce_bwd", _p(logits), _p(labels), _p(ctx.class_w), _p(ws), _p(g), _p(dl), b, _c_i64(h * w), k1, _c_i64(st[0]),
-             _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags, _c_i64(ctx.ign), _stream())
+        call("mia_topk_ce_bwd", _p(logits), _p(labels), _p(ctx.class_w), _p(ws), _p(g), _p(dl), b, _c_i64(h * w), k1,
+             *_strides_i64(st), *_strides_i64(gst), ctx.flags, _c_i64(ctx.ign), _stream())
         return dl, None, None, None, None
 
 
@@ -1472,12 +1474,7 @@ class RegionLossFn(torch.autograd.Function):
         _need_dev(logits, target, bits, pos_weight)
         if logits.ndim != 4:
             raise NotImplementedError("the HIP region loss implements 2-D inputs [B, C, H, W]")
-        if logits.dtype != torch.float32:
-            logits = logits.float()
-        st = _pix_strides(logits)
-        if st is None:
-            logits = logits.contiguous()
-            st = _pix_strides(logits)
+        logits, st = _loss_logits(logits)
         b, c, h, w = logits.shape
         if c > REGLOSS_MAX_CHANNELS:
             raise NotImplementedError(f"the HIP region loss implements up to {REGLOSS_MAX_CHANNELS} channels, got {c}")
@@ -1511,20 +1508,19 @@ class RegionLossFn(torch.autograd.Function):
                 raise MiaError(f"pos_weight: {pos_weight.numel()} values for {c} channels")
             pos_weight = pos_weight.detach().to(device=logits.device, dtype=torch.float32).reshape(c).contiguous()
         hw = h * w
-        slabs = max(1, min(256, hw // 8192))
+        slabs = _loss_slabs(hw)
         dev = logits.device
         ws = torch.empty((lib().mia_region_loss_workspace(b, c, slabs) + 1) // 2, device=dev, dtype=torch.float64)  # 8-byte aligned
         coef = torch.empty(b * c * 2 + 1, device=dev, dtype=torch.float32)  # every entry is written by the finalize kernel
         out = torch.empty(3, device=dev, dtype=torch.float32)
         counts = torch.empty((b, c, 3), device=dev, dtype=torch.int64)
         bad = _bad_flags(dev)
-        call("mia_region_loss_fwd", _p(logits), _p(target), _p(bits), n_labels, _p(pos_weight), b, _c_i64(hw), c, _c_i64(st[0]),
-             _c_i64(st[1]), _c_i64(st[2]), flags, _c_i64(ign), _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws),
-             _p(coef), _p(out), _p(counts), _p(bad), _stream())
+        call("mia_region_loss_fwd", _p(logits), _p(target), _p(bits), n_labels, _p(pos_weight), b, _c_i64(hw), c,
+             *_strides_i64(st), flags, _c_i64(ign), _c_float(smooth), _c_float(dice_w), _c_float(ce_w), slabs, _p(ws), _p(coef),
+             _p(out), _p(counts), _p(bad), _stream())
         ctx.save_for_backward(logits, target, coef)
         ctx.bits, ctx.pos_weight = bits, pos_weight
         ctx.flags, ctx.ign, ctx.st, ctx.n_labels = flags, ign, st, n_labels
-        DiceCEFn.last_bad_label = bad  # one sticky verdict per device, read by check_labels()
         RegionLossFn.last_out = out
         RegionLossFn.last_counts = counts
         return out[which]
@@ -1533,12 +1529,10 @@ class RegionLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         logits, target, coef = ctx.saved_tensors
         b, c, h, w = logits.shape
-        dl = torch.empty_like(logits)  # preserves (dense) strides
-        gst = _pix_strides(dl)
-        g = gout.reshape(1).float().contiguous()
+        dl, gst, g = _loss_bwd_begin(logits, gout)
         st = ctx.st
         call("mia_region_loss_bwd", _p(logits), _p(target), _p(ctx.bits), ctx.n_labels, _p(ctx.pos_weight), _p(coef), _p(g), _p(dl), b,
-             _c_i64(h * w), c, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _c_i64(gst[0]), _c_i64(gst[1]), _c_i64(gst[2]), ctx.flags,
+             _c_i64(h * w), c, *_strides_i64(st), *_strides_i64(gst), ctx.flags,
              _c_i64(ctx.ign), _stream())
         return dl, None, None, None, None, None, None, None, None, None
 

@@ -1,6 +1,6 @@
 """Float64 restatement of the tail of a training step (test infrastructure only): the 1x1 segmentation head and the head fused with
-the last block's norm + LeakyReLU (csrc/head_loss.hip), the norm backward fed by the head (csrc/norm.hip, mia_norm_act_bwd_head[_w])
-and the fused Dice + cross-entropy loss, plus the seeded case tables that tests/test_head_loss_host.py (CPU) and
+the last block's norm + LeakyReLU (csrc/head.hip), the norm backward fed by the head (csrc/norm.hip, mia_norm_act_bwd_head[_w])
+and the fused Dice + cross-entropy loss (csrc/dice_ce.hip), plus the seeded case tables that tests/test_head_loss_host.py (CPU) and
 tests/test_gpu_head_loss.py (GPU) share.  Activations are NHWC with the pixels flattened, [N, P, C]; logits and their gradient
 are [N, P, K].
 

@@ -1,5 +1,5 @@
-"""GPU checks of the tail of a training step at kernel level: the 1x1 head, the head fused with the last block's norm + LeakyReLU,
-the Dice + CE loss (csrc/head_loss.hip) and the norm backward fed by the head (csrc/norm.hip, mia_norm_act_bwd_head[_w]) against the
+"""GPU checks of the tail of a training step at kernel level: the 1x1 head, the head fused with the last block's norm + LeakyReLU
+(csrc/head.hip), the Dice + CE loss (csrc/dice_ce.hip) and the norm backward fed by the head (csrc/norm.hip, mia_norm_act_bwd_head[_w]) against the
 float64 restatement in tests/_head_loss_ref.py, called through the C ABI (mia_hip.call / ops._p).  Inputs are seeded and exactly
 representable in their storage types on both sides; every output buffer (the gaps of padded layouts included) starts as NaN, the
 gaps must still be NaN afterwards and every element a kernel owns finite.
