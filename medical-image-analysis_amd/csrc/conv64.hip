@@ -24,17 +24,11 @@
 // destinations (two = the input gradient of a decoder block whose input was [skip | up]: one launch per destination over
 // the same input), packed weights [9][64 or 128][64], 16-byte aligned pointers, per-image tensors < 2 GiB.
 #include "conv_common.h"
+#include "lds_dma.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define SENT 0xFFFFFFF0u /* always beyond num_records */
-
 namespace {
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 constexpr int C = 64;             // channels in == out
 constexpr int TH = 16, TW = 16;   // output tile
@@ -45,28 +39,10 @@ constexpr int LDS_BYTES = 8 * NPA * 16;
 
 struct Tile { int img, ty, tx; };
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-// two floats -> packed bf16 pair (low = a): ONE v_cvt_pk_bf16_f32 (RNE, NaN stays NaN)
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
-
 // s1 += v; s2 += v * v as two single-issue VALU instructions (hipcc otherwise SLP-packs the pair into mov + mul + v_pk_add_f32,
 // three instructions of which the packed one costs double beside MFMAs)
 __device__ __forceinline__ void stat_acc(float& s1, float& s2, float v) {
   asm volatile("v_add_f32 %0, %2, %0\n\tv_fmac_f32 %1, %2, %2" : "+v"(s1), "+v"(s2) : "v"(v));
-}
-
-// sum over the 16 lanes of a DPP row (every lane gets the total): 4 v_add_f32 with DPP operands, no LDS crossbar
-__device__ __forceinline__ float row16_sum(float v) {
-  int iv;
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false));   // lane ^ 1
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false));   // lane ^ 2
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false));  // row_mirror
-  return v;
 }
 
 }  // namespace

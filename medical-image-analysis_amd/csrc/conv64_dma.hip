@@ -19,45 +19,10 @@
 // Contract (conv64_dma_eligible, otherwise conv64 / conv_mma_fast run): bf16, MODE_G3S1, c1 = 64, c2 = 0, o1 = 64, o2 in {0, 64},
 // packed weights [9][npad = o1 + o2][64], Hout > 8, 16-byte aligned pointers, per-image tensors < 2 GiB.
 #include "conv_common.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define CD_SENT 0xFFFFFFF0u
-
-__device__ __forceinline__ i32x4 rsrc_words(const void* p, unsigned bytes) {
-  const unsigned long long addr = (unsigned long long)p;
-  i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)addr);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-// One LDS-DMA piece (64 lanes x 16 B -> lds_dst + 16 L); see conv_bt.hip::dma16.
-__device__ __forceinline__ void dma16(i32x4 rsrc, unsigned voff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" : : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row
-  int iv;
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false));
-  return v;
-}
 
 constexpr int C = 64, TH = 16, TW = 16, IH = TH + 2, IW = TW + 2;
 constexpr int NPIX = IH * IW;            // 324 halo pixels
@@ -139,7 +104,7 @@ __global__ __launch_bounds__(512, 2) void conv64_dma_kernel(const ConvArgs a, in
   const bf16_t* in = static_cast<const bf16_t*>(a.in1);
 
   // ---- DMA lane constants.  Piece k = wave + 8 j covers halo pixels 8 k .. 8 k + 7; lane L = (pixel L >> 3, slot L & 7)
-  unsigned toff[PPW];   // offset from the tile's first halo pixel (interior tiles), CD_SENT for padding pixels
+  unsigned toff[PPW];   // offset from the tile's first halo pixel (interior tiles), SENT for padding pixels
   unsigned rc[PPW];     // row | col << 8 of this lane's pixel (border tiles)
 #pragma unroll
   for (int j = 0; j < PPW; ++j) {
@@ -147,7 +112,7 @@ __global__ __launch_bounds__(512, 2) void conv64_dma_kernel(const ConvArgs a, in
     const int row = p / IW, col = p - row * IW;
     const int chunk = (lane & 7) ^ ((col >> 1) & 7);
     rc[j] = (unsigned)(row | (col << 8) | (chunk << 16) | ((p < NPIX ? 1 : 0) << 24));
-    toff[j] = p < NPIX ? (unsigned)(((row * a.Win + col) * C + chunk * 8) * 2) : CD_SENT;
+    toff[j] = p < NPIX ? (unsigned)(((row * a.Win + col) * C + chunk * 8) * 2) : SENT;
   }
   auto issue_piece = [&](const Tile& t, unsigned stage_base, auto jc) __attribute__((always_inline)) {
     constexpr int j = decltype(jc)::value;
@@ -158,13 +123,13 @@ __global__ __launch_bounds__(512, 2) void conv64_dma_kernel(const ConvArgs a, in
     const unsigned dst = __builtin_amdgcn_readfirstlane(stage_base + k * 1024);
     if (interior) {
       const i32x4 rs = rsrc_words(in + ((size_t)t.img * ipix + (size_t)iy0 * a.Win + ix0) * C, (unsigned)(IH * a.Win * C * 2));
-      dma16(rs, toff[j], dst);
+      dma16<4>(rs, toff[j], dst);
     } else {
       const i32x4 rs = rsrc_words(in + (size_t)t.img * ipix * C, img_bytes);
       const int row = rc[j] & 0xFF, col = (rc[j] >> 8) & 0xFF, chunk = (rc[j] >> 16) & 0xFF;
       const int gy = iy0 + row, gx = ix0 + col;
       const bool ok = ((rc[j] >> 24) != 0) & ((unsigned)gy < (unsigned)a.Hin) & ((unsigned)gx < (unsigned)a.Win);
-      dma16(rs, ok ? (unsigned)(((gy * a.Win + gx) * C + chunk * 8) * 2) : CD_SENT, dst);
+      dma16<4>(rs, ok ? (unsigned)(((gy * a.Win + gx) * C + chunk * 8) * 2) : SENT, dst);
     }
   };
 #define CD_PIECE(T, S, J) issue_piece(T, S, std::integral_constant<int, J>{})
@@ -244,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void conv64_dma_kernel(const ConvArgs a, in
       const auto r1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       const u32x4 d = {r0[0], r1[0], r0[1], r1[1]};
       const bool ok = g.full || (g.colok && (g.oy0 + m + qodd < a.Hout));
-      const unsigned voff = ok ? obase + (unsigned)(m * row_bytes) : CD_SENT;
+      const unsigned voff = ok ? obase + (unsigned)(m * row_bytes) : SENT;
       __builtin_amdgcn_raw_buffer_store_b128(d, rso, (int)voff, 0, 0);
     }
   };

@@ -26,47 +26,11 @@
 // Contract (conv_bt_eligible, otherwise conv_mma_fast runs): bf16, MODE_G3S1, Hout > 8, c1 % 32 == 0, c2 in {0, c1},
 // (o1 + o2) % NCH == 0 and o1 % NCH == 0, 16-byte aligned pointers, per-image tensors and the packed weights < 2 GiB.
 #include "conv_common.h"
+#include "lds_dma.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define BT_SENT 0xFFFFFFF0u /* always beyond num_records: loads return zero, stores are dropped */
-
-__device__ __forceinline__ i32x4 rsrc_words(const void* p, unsigned bytes) {
-  const unsigned long long addr = (unsigned long long)p;
-  i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)addr);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-// One LDS-DMA piece: 64 lanes x 16 bytes, lane L lands at lds_dst + 16 L.  M0 (the LDS base) is written and read inside this
-// one statement (hipcc uses M0 for nothing else in this kernel); s_nop 4 covers the VALU-written-SGPR -> VMEM hazard of the
-// descriptor / offset operands, which hipcc does not pad inside an asm statement.
-__device__ __forceinline__ void dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
-  asm volatile("s_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory", "m0");
-}
-
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row
-  int iv;
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false));
-  return v;
-}
 
 constexpr int TW = 32, TH = 16, IW = TW + 2, IH = TH + 2;
 constexpr int NPIX = IH * IW;                  // 612 halo pixels
@@ -110,9 +74,6 @@ extern "C" int mia_conv_bt_debug_read(unsigned long long* host_out) {
 #define BSTAMP(var) do { } while (0)
 #define BACC(dst, t1, t0) do { } while (0)
 #endif
-
-// wait until at most N vector-memory operations of this wave are outstanding
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct BtWork { int img, ty, tx, n0; };
 
@@ -192,7 +153,7 @@ __global__ __launch_bounds__(512, 2) void conv_bt_kernel(const ConvArgs a, int p
       const int gy = oy0 - 1 + row, gx = ox0 - 1 + col;
       const bool ok = (p < NPIX) & ((unsigned)gy < (unsigned)a.Hin) & ((unsigned)gx < (unsigned)a.Win);
       const int chunk = (lv & 3) ^ ((col >> 2) & 3);
-      ioff[j] = ok ? (unsigned)(((gy * a.Win + gx) * a.c1 + chunk * 8) * 2) : BT_SENT;
+      ioff[j] = ok ? (unsigned)(((gy * a.Win + gx) * a.c1 + chunk * 8) * 2) : SENT;
     }
   };
   // weight piece i = wave + 8 jj = (tap row ta, 16-channel block j): lane L = (channel L >> 2, slot L & 3).  wsoff[tb][jj] =
@@ -220,7 +181,7 @@ __global__ __launch_bounds__(512, 2) void conv_bt_kernel(const ConvArgs a, int p
   };
   auto issue_w1 = [&](unsigned wlane, int chunk, int tb, int jj) __attribute__((always_inline)) {
     if (!G::WDUMMY || w_ok[jj])  // a wave without a piece in the last round issues nothing: its waits count one piece less (wait_w)
-      dma16(rsw, wlane, wsoff[tb][jj] + (unsigned)(chunk * 64), __builtin_amdgcn_readfirstlane(lds0 + G::RING + tb * SLOT + (wave + 8 * jj) * 1024));
+      dma16<4>(rsw, wlane, wsoff[tb][jj] + (unsigned)(chunk * 64), __builtin_amdgcn_readfirstlane(lds0 + G::RING + tb * SLOT + (wave + 8 * jj) * 1024));
   };
   auto issue_w = [&](int chunk, int tb) __attribute__((always_inline)) {
     const unsigned wlane = make_wlane();
@@ -232,14 +193,14 @@ __global__ __launch_bounds__(512, 2) void conv_bt_kernel(const ConvArgs a, int p
     const bool second = c0 >= a.c1;  // uniform: chunks never straddle the two sources
     const unsigned soff = (unsigned)((second ? c0 - a.c1 : c0) * 2);
     const unsigned dst = lds0 + buf * IMG_BYTES + (wave + 8 * j) * 1024;
-    dma16(second ? irs2 : irs1, ioff[j], __builtin_amdgcn_readfirstlane(soff), __builtin_amdgcn_readfirstlane(dst));
+    dma16<4>(second ? irs2 : irs1, ioff[j], __builtin_amdgcn_readfirstlane(soff), __builtin_amdgcn_readfirstlane(dst));
   };
   // bias of a channel block: NCH floats, lanes 0 .. NCH / 4 - 1 (every wave writes the same bytes; a wave reads them after
   // its OWN piece has landed)
   auto issue_bias = [&](int n0) __attribute__((always_inline)) {
     const int lane = lane_id();
-    const unsigned blane = lane < NCH / 4 ? (unsigned)(lane * 16) : BT_SENT;
-    dma16(rsb, blane, __builtin_amdgcn_readfirstlane((unsigned)(n0 * 4)), __builtin_amdgcn_readfirstlane(lds0 + G::BIAS));
+    const unsigned blane = lane < NCH / 4 ? (unsigned)(lane * 16) : SENT;
+    dma16<4>(rsb, blane, __builtin_amdgcn_readfirstlane((unsigned)(n0 * 4)), __builtin_amdgcn_readfirstlane(lds0 + G::BIAS));
   };
 
   // ---- fragment read addresses (bytes from the start of LDS), computed per step in compute()
@@ -368,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void conv_bt_kernel(const ConvArgs a, int p
         const u32x4 d = {pack_bf16x2(acc[m][2 * k][0], acc[m][2 * k][1]), pack_bf16x2(acc[m][2 * k][2], acc[m][2 * k][3]),
                          pack_bf16x2(acc[m][2 * k + 1][0], acc[m][2 * k + 1][1]), pack_bf16x2(acc[m][2 * k + 1][2], acc[m][2 * k + 1][3])};
         const bool ok = o.full || (o.colok && (o.wy0 + m < a.Hout));
-        const unsigned voff = ok ? o.obase + (unsigned)(m * o.row_bytes + k * 64) : BT_SENT;
+        const unsigned voff = ok ? o.obase + (unsigned)(m * o.row_bytes + k * 64) : SENT;
         __builtin_amdgcn_raw_buffer_store_b128(d, o.rso, (int)voff, 0, 0);
       }
     } else {
@@ -383,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void conv_bt_kernel(const ConvArgs a, int p
           const auto r1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
           const u32x4 d = {r0[0], r1[0], r0[1], r1[1]};
           const bool ok = o.full || (o.colok && (o.wy0 + m - 1 + qodd < a.Hout));
-          const unsigned voff = ok ? o.obase + (unsigned)((m - 1) * o.row_bytes + ct * 32) : BT_SENT;
+          const unsigned voff = ok ? o.obase + (unsigned)((m - 1) * o.row_bytes + ct * 32) : SENT;
           __builtin_amdgcn_raw_buffer_store_b128(d, o.rso, (int)voff, 0, 0);
         }
       }

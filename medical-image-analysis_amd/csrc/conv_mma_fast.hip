@@ -11,13 +11,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define SENT 0xFFFFFFF0u /* always beyond num_records */
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
+#include "lds_dma.h"
 
 // WC = 2 (stride-2 3x3 forward, bf16): 512 threads, the eight waves are 4 row groups x 2 halves of a 128-channel block on a
 // 16-row tile -- each wave owns 4 x 4 accumulators (8 fragment reads per 16 MFMAs instead of 6 per 8: the 256-thread

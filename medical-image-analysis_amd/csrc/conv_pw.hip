@@ -35,44 +35,17 @@
 // Contract (conv_pw_eligible, otherwise the tile kernel runs): bf16, one source, one destination, no statistics; channels per
 // tap of the input % 64 == 0, K >= 128, N % 128 == 0, npad / kpad unpadded, tensors < 4 GiB, 16-byte aligned pointers.
 #include "conv_common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef __attribute__((address_space(3))) unsigned char lds_u8;
-#define PW_SENT 0xFFFFFFF0u /* always beyond num_records: loads return zero, stores are dropped */
 
-__device__ __forceinline__ i32x4 pw_rsrc_words(const void* p, unsigned bytes) {
-  const unsigned long long addr = (unsigned long long)p;
-  i32x4 r;
-  r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)addr);
-  r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
-  r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-  r.w = 0x00020000;
-  return r;
-}
-// One LDS-DMA piece: 64 lanes x 16 bytes, lane L lands at lds_dst + 16 L (see conv_bt.hip::dma16 for the M0 / s_nop notes).
-__device__ __forceinline__ void pw_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
-  soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);        // wave-uniform by construction; tells hipcc so
+// dma16<4> (lds_dma.h) with `soff` and `lds_dst` declared wave-uniform: they are by construction; this tells hipcc so
+__device__ __forceinline__ void dma16_uniform(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
+  soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
   lds_dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_dst);
-  asm volatile("s_mov_b32 m0, %3\n\ts_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory", "m0");
-}
-template <int N> __device__ __forceinline__ void pw_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-typedef float pw_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 pw_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pw_pack(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(pw_f32x2{a, b}, pw_bf16x2));
-}
-
-__device__ __forceinline__ float pw_row16_sum(float v) {  // sum over the 16 lanes of a DPP row, left in every lane
-  int iv;
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0xB1, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x4E, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x141, 0xF, 0xF, false));
-  iv = __builtin_bit_cast(int, v); v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(iv, iv, 0x140, 0xF, 0xF, false));
-  return v;
+  dma16<4>(rsrc, voff, soff, lds_dst);
 }
 
 constexpr int PW_TM = 256, PW_TN = 128;
@@ -99,10 +72,10 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
   const int cpt = cin >> 6;                 // 64-wide stages per tap (MODE_G2S2)
 
   const size_t in_bytes = (size_t)a.N * a.Hin * a.Win * a.c1 * 2, out_bytes = (size_t)a.N * a.Hout * a.Wout * a.o1 * 2;
-  const i32x4 rsA = pw_rsrc_words(a.in1, (unsigned)in_bytes);
-  const i32x4 rsW = pw_rsrc_words(a.wp, (unsigned)((size_t)4 * a.npad * a.kpad * 2));
-  const i32x4 rsB = pw_rsrc_words(BIAS ? (const void*)a.bias : a.wp, BIAS ? (unsigned)(a.o1 * 4) : 0u);
-  const i32x4 rsW9 = pw_rsrc_words(a.wp, (unsigned)((size_t)9 * a.npad * a.kpad * 2));  // S2: nine taps
+  const i32x4 rsA = rsrc_words(a.in1, (unsigned)in_bytes);
+  const i32x4 rsW = rsrc_words(a.wp, (unsigned)((size_t)4 * a.npad * a.kpad * 2));
+  const i32x4 rsB = rsrc_words(BIAS ? (const void*)a.bias : a.wp, BIAS ? (unsigned)(a.o1 * 4) : 0u);
+  const i32x4 rsW9 = rsrc_words(a.wp, (unsigned)((size_t)9 * a.npad * a.kpad * 2));  // S2: nine taps
   const rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(a.out1, 0, (int)(unsigned)out_bytes, 0x00020000);
 
   struct Item { int m0, n0; };
@@ -153,7 +126,7 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
   const int lr = lane >> 3;
   const unsigned uA = (unsigned)((lane & 7) ^ ((4 * wave + (lane >> 4)) & 7));
   const unsigned uB = (unsigned)((lane & 7) ^ (((lane >> 4) & 1) | ((wave & 3) << 1)));
-  unsigned va[4], vb[2], vbias = PW_SENT, vmask = 0;
+  unsigned va[4], vb[2], vbias = SENT, vmask = 0;
   int i_n0 = 0, i_nk = nk, ipos = 0;  // T3: the fetched item's column base, stage count, current window position
   unsigned i_pm = 1;                  //     and remaining-position mask
   auto setup_issue = [&](int w) __attribute__((always_inline)) {
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
         const unsigned bits = (i + 1 < a.Hin ? 1u : 0u) | (j + 1 < a.Win ? 2u : 0u);
         vmask = k == 0 ? bits : (vmask | (bits << (2 * k)));
       } else { const int j = p % wco; base = (unsigned)(4 * p - 2 * j) * (unsigned)(cin * 2); }  // fine pixel (n, 2i, 2j)
-      va[k] = p < mtot ? base + uA * 16u : PW_SENT;
+      va[k] = p < mtot ? base + uA * 16u : SENT;
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -183,7 +156,7 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
       vb[k] = (unsigned)row * kpitch + uB * 16u;
     }
     if (T3) { i_n0 = it.n0; i_nk = t3_nk(it.n0); i_pm = t3_posmask(it.n0); ipos = __builtin_ctz(i_pm); }
-    if (BIAS) vbias = lane < 32 ? (unsigned)((it.n0 + 4 * lane) % a.o1) * 4u : PW_SENT;
+    if (BIAS) vbias = lane < 32 ? (unsigned)((it.n0 + 4 * lane) % a.o1) * 4u : SENT;
   };
   int wi = blockIdx.x, ki = 0, itap = 0, icc = 0, ita = 0, itb = 0, islot = 0, ibias = 0;
   bool ihave = T3 ? t3_live(wi) : wi < nwork;
@@ -204,25 +177,25 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
       unsigned v = va[k];
       if (S2) {  // tap (ita, itb): a signed pixel offset, rows / columns outside the image read zeros
         const int toff = ((ita - 1) * a.Win + (itb - 1)) * (cin * 2) + icc * 128;
-        const bool ok = ((vmask >> (6 * k + ita)) & (vmask >> (6 * k + 3 + itb)) & 1u) != 0u && v != PW_SENT;
-        v = ok ? (unsigned)((int)v + toff) : PW_SENT;
+        const bool ok = ((vmask >> (6 * k + ita)) & (vmask >> (6 * k + 3 + itb)) & 1u) != 0u && v != SENT;
+        v = ok ? (unsigned)((int)v + toff) : SENT;
       }
       if (T3) {  // position (dh, dw): the row below / the column to the right must exist
         const unsigned vb2 = vmask >> (2 * k);
         const bool ok = (!(ipos & 2) || (vb2 & 1u)) && (!(ipos & 1) || (vb2 & 2u));
-        v = ok ? v : PW_SENT;
+        v = ok ? v : SENT;
       }
-      pw_dma16(rsA, v, soffA, dst + (unsigned)k * 8192u);
+      dma16_uniform(rsA, v, soffA, dst + (unsigned)k * 8192u);
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       if (T3) {  // the half's class picks the tap of this position, or zeros when it has none
         const int tap = t3_tap(t3_cls(i_n0, k), ipos);
-        pw_dma16(rsW9, tap >= 0 ? vb[k] : PW_SENT, soffB + (unsigned)(tap >= 0 ? tap : 0) * (unsigned)a.npad * kpitch, dst + PW_A + (unsigned)k * 8192u);
-      } else pw_dma16(S2 ? rsW9 : rsW, vb[k], soffB, dst + PW_A + (unsigned)k * 8192u);
+        dma16_uniform(rsW9, tap >= 0 ? vb[k] : SENT, soffB + (unsigned)(tap >= 0 ? tap : 0) * (unsigned)a.npad * kpitch, dst + PW_A + (unsigned)k * 8192u);
+      } else dma16_uniform(S2 ? rsW9 : rsW, vb[k], soffB, dst + PW_A + (unsigned)k * 8192u);
     }
     int cnt = 6;
-    if (BIAS && ki == 0) { pw_dma16(rsB, vbias, 0u, lds0 + PW_BIAS + (unsigned)ibias * 1024u); ibias ^= 1; cnt = 7; }
+    if (BIAS && ki == 0) { dma16_uniform(rsB, vbias, 0u, lds0 + PW_BIAS + (unsigned)ibias * 1024u); ibias ^= 1; cnt = 7; }
     islot = islot == PW_NSTAGE - 1 ? 0 : islot + 1;
     ++ki;
     if (!TR) {
@@ -247,7 +220,7 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
 
   issue_next();
   issue_next();  // nk >= 2: the first item's second stage, 6 pieces
-  pw_wait_vm<6>();
+  wait_vm<6>();
   __builtin_amdgcn_s_barrier();
 
   int cslot = 0, cbias = 0, st_m0 = 0, st_n0 = 0;
@@ -284,9 +257,9 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
                                                                   acc[ct][pf], 0, 0, 0);
       cslot = cslot == PW_NSTAGE - 1 ? 0 : cslot + 1;
       // own pieces of the stage after next may stay in flight (and the previous item's stores, issued between the two)
-      if (cnt == 0) pw_wait_vm<0>();
-      else if (after_epilogue) { if (cnt == 7) pw_wait_vm<7 + PW_NSTORE>(); else pw_wait_vm<6 + PW_NSTORE>(); }
-      else { if (cnt == 7) pw_wait_vm<7>(); else pw_wait_vm<6>(); }
+      if (cnt == 0) wait_vm<0>();
+      else if (after_epilogue) { if (cnt == 7) wait_vm<7 + PW_NSTORE>(); else wait_vm<6 + PW_NSTORE>(); }
+      else { if (cnt == 7) wait_vm<7>(); else wait_vm<6>(); }
       after_epilogue = false;
 
       if (kc == nk_cur - 1) {  // ---- epilogue: 8 consecutive channels per lane and fragment pair, 16-byte stores
@@ -309,12 +282,12 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
         // operations it knows about (the LDS-DMA pieces are invisible to it).
         u32x4 prev[2][4];
         if (T3 && a.acc_out) {
-          pw_wait_vm<0>();
+          wait_vm<0>();
 #pragma unroll
           for (int pr = 0; pr < 2; ++pr)
 #pragma unroll
             for (int pf = 0; pf < 4; ++pf) {
-              const unsigned vo = t3pix[pf] != 0xFFFFFFFFu ? (t3pix[pf] * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : PW_SENT;
+              const unsigned vo = t3pix[pf] != 0xFFFFFFFFu ? (t3pix[pf] * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : SENT;
               prev[pr][pf] = __builtin_amdgcn_raw_buffer_load_b128(rsO, (int)vo, 0, 0);
             }
         }
@@ -338,8 +311,8 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
             unsigned pix;
             if (TR) { const int j = p % wco; pix = (unsigned)(4 * p - 2 * j) + tapoff; }
             else pix = (unsigned)p;
-            unsigned voff = p < mtot ? (pix * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : PW_SENT;
-            if (T3) voff = t3pix[pf] != 0xFFFFFFFFu ? (t3pix[pf] * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : PW_SENT;
+            unsigned voff = p < mtot ? (pix * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : SENT;
+            if (T3) voff = t3pix[pf] != 0xFFFFFFFFu ? (t3pix[pf] * (unsigned)a.o1 + (unsigned)(co0 + 32 * pr + 8 * q)) * 2u : SENT;
             const f32x4 lo = acc[2 * pr][pf], hi = acc[2 * pr + 1][pf];
             float v[8];
 #pragma unroll
@@ -356,14 +329,14 @@ __global__ __launch_bounds__(512, 2) void conv_pw_kernel(const ConvArgs a, int m
               for (int e = 0; e < 8; ++e) { s1[e] += v[e]; s2[e] += v[e] * v[e]; }
             }
             u32x4 d;
-            d.x = pw_pack(v[0], v[1]); d.y = pw_pack(v[2], v[3]); d.z = pw_pack(v[4], v[5]); d.w = pw_pack(v[6], v[7]);
+            d.x = pack_bf16x2(v[0], v[1]); d.y = pack_bf16x2(v[2], v[3]); d.z = pack_bf16x2(v[4], v[5]); d.w = pack_bf16x2(v[6], v[7]);
             __builtin_amdgcn_raw_buffer_store_b128(d, rsO, (int)voff, 0, 0);
           }
           if (S2 && a.stats != nullptr) {  // per-wave sums of its 64 pixels: DPP row sums over the 16 pixel lanes
             float* red = reinterpret_cast<float*>(smem + PW_RED) + (wave * 64 + 32 * pr + 8 * q) * 2;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              const float t1 = pw_row16_sum(s1[e]), t2 = pw_row16_sum(s2[e]);
+              const float t1 = row16_sum(s1[e]), t2 = row16_sum(s2[e]);
               if (r == 0) { red[2 * e] = t1; red[2 * e + 1] = t2; }
             }
           }

@@ -13,7 +13,7 @@ OBJ = os.path.join(HERE, "_obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc"]
 # Kernels that issue LDS-DMA in inline asm and count `vmcnt` by hand: a register spill would add compiler-made scratch
 # traffic to the same counter and break the count, so the build fails unless their scratch size is 0.
-COUNTED_VMCNT = {"conv_bt.hip": ("conv_bt_kernel",), "conv_pw.hip": ("conv_pw_kernel",), "conv64_dma.hip": ("conv64_dma_kernel",), "conv_wgrad.hip": ("wgrad_bf16_dma_kernel", "wgrad_bf16_dma96_kernel", "wgrad_bf16_bt_kernel", "wgrad_bf16_bt_s2_kernel", "wgrad_bf16_bt_t2_kernel")}
+COUNTED_VMCNT = {"conv_bt.hip": ("conv_bt_kernel",), "conv_pw.hip": ("conv_pw_kernel",), "conv64_dma.hip": ("conv64_dma_kernel",), "wgrad_ring.hip": ("wgrad_bf16_dma_kernel", "wgrad_bf16_dma96_kernel"), "wgrad_bt.hip": ("wgrad_bf16_bt_kernel", "wgrad_bf16_bt_s2_kernel", "wgrad_bf16_bt_t2_kernel")}
 
 
 def sources():
@@ -51,6 +51,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     srcs = sources()
+    unknown = set(COUNTED_VMCNT) - {os.path.basename(s) for s in srcs}
+    if unknown:
+        raise RuntimeError(f"COUNTED_VMCNT names no source file: {sorted(unknown)} (a renamed file would lose its no-scratch guard)")
     jobs = []
     for s in srcs:
         o = os.path.join(OBJ, os.path.basename(s)[:-4] + ".o")

@@ -132,7 +132,7 @@ def test_conv3x3_fwd_dgrad_wgrad(case, stride, dtype):
 @pytest.mark.parametrize("case", [(2, 96, 0, 96, 24, 40), (1, 96, 96, 96, 19, 33), (1, 192, 0, 96, 12, 52), (3, 96, 0, 192, 9, 17), (1, 96, 96, 96, 4, 16),
                                   (1, 288, 0, 96, 11, 21), (2, 96, 0, 96, 3, 5)])
 def test_weight_gradient_on_96_wide_blocks(case):
-    """`wgrad_bf16_dma96_kernel` (csrc/conv_wgrad.hip): 3x3 stride-1 bf16 layers whose channel counts are multiples of 96 and not of 64
+    """`wgrad_bf16_dma96_kernel` (csrc/wgrad_ring.hip): 3x3 stride-1 bf16 layers whose channel counts are multiples of 96 and not of 64
     (cfg5's level 0) run ONE 96 x 96 block per pixel tile on the LDS-DMA ring (768 threads, 192-byte-row images) where the 64-wide kernel
     needs 2 x 2 blocks.  One and two sources, several blocks per dimension, ragged and tiny images (tiles hanging over every border);
     bf16 inputs quantised on both sides, so the result differs from the fp32 reference by summation order only.  `mia_wgrad_plan` must
@@ -663,6 +663,66 @@ def test_kernel_selection_knobs_do_not_change_results(knob):
     assert torch.allclose(on[3], off[3], rtol=1e-4, atol=1e-4 * off[3].abs().max().item())
 
 
+# One case per weight-gradient launch family that decodes its block through WgCols (csrc/wgrad_common.h):
+# (mode, c1, c2, cdy, output rows, output columns, options).  Batch 2: 2 x ceil(rows / tile height) x 2 = 16 pixel tiles, ragged in
+# both directions, and every case has far fewer column blocks than the machine has slots, so the split count is the tile count, 16.
+WGRAD_XCD_CASES = {
+    "bt_s1": ("3S1", 128, 0, 128, 14, 20, {}),        # wgrad_bf16_bt_kernel
+    "bt_s2": ("3S2", 64, 0, 128, 14, 20, {}),         # wgrad_bf16_bt_s2_kernel
+    "bt_t2": ("2S2", 64, 0, 128, 14, 20, {}),         # wgrad_bf16_bt_t2_kernel: ConvTranspose2d(128 -> 64), x = the fine gradient
+    "dma96": ("3S1", 96, 96, 96, 14, 20, {}),         # wgrad_bf16_dma96_kernel
+    "dma": ("3S1", 64, 0, 64, 14, 20, {}),            # wgrad_bf16_dma_kernel
+    "2wg": ("3S1", 64, 0, 64, 30, 20, {"wgrad_dma": 0}),  # wgrad_bf16_2wg_kernel (8-row tiles)
+    "fast_s2": ("3S2", 32, 0, 64, 14, 20, {}),        # wgrad_bf16_fast_kernel<MODE_W3S2>
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(WGRAD_XCD_CASES))
+def test_wgrad_xcd_order_is_bit_identical_per_family(case):
+    """Option wgrad_xcd only permutes which workgroup computes which (column block, split index): each workgroup writes its own
+    slab and mia_wgrad_reduce adds the slabs in a fixed order, so the weight gradient is bit-identical with the option on and off
+    (read from the code).  The XCD order is taken only when the split count is a multiple of 8: the test recomputes the count
+    ops.conv_wgrad picks and asserts that, so it cannot pass by not running the path."""
+    import ctypes
+    import mia_hip
+    from mia_hip import BF16, WGRAD_2S2, WGRAD_3S1, WGRAD_3S2, ops
+    mname, c1, c2, cdy, hy, wy, opts = WGRAD_XCD_CASES[case]
+    mode = {"3S1": WGRAD_3S1, "3S2": WGRAD_3S2, "2S2": WGRAD_2S2}[mname]
+    ks = 2 if mode == WGRAD_2S2 else 3
+    hx, wx = (hy, wy) if mode == WGRAD_3S1 else (2 * hy, 2 * wy)
+    dev = _dev()
+    g = torch.Generator().manual_seed(23)
+    x1 = torch.randn(2, hx, wx, c1, generator=g).to(dev).to(torch.bfloat16)
+    x2 = torch.randn(2, hx, wx, c2, generator=g).to(dev).to(torch.bfloat16) if c2 else None
+    dy = torch.randn(2, hy, wy, cdy, generator=g).to(dev).to(torch.bfloat16)
+    shape = (cdy, c1 + c2, ks, ks)
+    saved = {k: mia_hip.get_option(k) for k in ("wgrad_xcd", *opts)}
+    model = ops.WGRAD_KSPLIT_MODEL
+    try:
+        ops.WGRAD_KSPLIT_MODEL = False  # (the cost model gives problems this small ONE slice)
+        for k, v in opts.items():
+            mia_hip.set_option(k, v)
+        # the split count, with the arithmetic of ops.conv_wgrad
+        pb, pt, ph = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        ops.call("mia_wgrad_plan", mode, BF16, c1, c2, cdy, -(-cdy // 64) * 64, hy, ctypes.byref(pb), ctypes.byref(pt), ctypes.byref(ph))
+        ntiles = 2 * -(-hy // ph.value) * -(-wy // 16)
+        ksplit = max(1, min(ntiles, -(-(ops.WGRAD_TARGET_BLOCKS or pt.value) // pb.value), 1024))
+        if 8 <= ksplit < ntiles:
+            ksplit -= ksplit % 8
+        assert ksplit >= 8 and ksplit % 8 == 0, (ksplit, ntiles, pb.value, pt.value, ph.value)
+        out = {}
+        for flag in (1, 0):
+            mia_hip.set_option("wgrad_xcd", flag)
+            out[flag] = ops.conv_wgrad(mode, x1, x2, dy, shape, cdy, c1 + c2).clone()
+    finally:
+        ops.WGRAD_KSPLIT_MODEL = model
+        for k, v in saved.items():
+            mia_hip.set_option(k, v)
+    assert out[0].abs().max().item() > 0
+    assert torch.equal(out[1], out[0])
+
+
 PW_CASES = [  # n, cin, cout, h, w (coarse): ConvTranspose2d(cin -> cout, 2, 2) on conv_pw_kernel -- 64 outputs (a 128-column block
     # spans two taps), ragged last pixel tile, pixel tiles not a multiple of 8 (column-block-slow item order), odd widths,
     # more items than CUs, K = 128 (two stages per item) and K = 1024
@@ -713,7 +773,7 @@ def test_conv_pw_matches_tile_kernel_and_reference(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", [(2, 128, 64, 64, 64), (1, 256, 128, 17, 23), (3, 128, 64, 9, 40), (1, 1024, 512, 8, 8), (1, 384, 192, 20, 12)])
 def test_wgrad_t2_matches_fast_kernel_and_reference(case):
-    """Option wgrad_t2 (csrc/conv_wgrad.hip::wgrad_bf16_bt_t2_kernel): the ConvTranspose2d 2x2 weight gradient on the 512-thread
+    """Option wgrad_t2 (csrc/wgrad_bt.hip::wgrad_bf16_bt_t2_kernel): the ConvTranspose2d 2x2 weight gradient on the 512-thread
     three-stage ring; fp32 slabs of exact bf16 products -> agreement with the 256-thread kernel and with autograd to fp32 summation
     order (reference: unet.py:142)."""
     import mia_hip

@@ -26,14 +26,14 @@ old = c64[c64.index("      const f32x2_t x = {__builtin_bit_cast(float, w << 16)
           c64.index("      o[d] = MASK ? (r & keep) : r;")]
 c64 = c64.replace(old, "      const unsigned r = nl_pair_scalar(w, sc[0], sc[1], sh[0], sh[1], a.nl_slope);\n")
 c64 = c64.replace("template <bool NL, bool CR>\n__global__", HELP + "template <bool NL, bool CR>\n__global__", 1)
-wg = open(os.path.join(CSRC, "conv_wgrad.hip")).read()
+wg = open(os.path.join(CSRC, "wgrad_ring.hip")).read()  # the file that holds wgrad_bf16_2wg_kernel
 old = wg[wg.index("            const nl_f32x2 x = {__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xFFFF0000u)};"):
          wg.index("          }\n        }\n        __builtin_amdgcn_sched_barrier(0);\n      }\n      if (!interior) {  // border tile: halo units outside the image go back to zero")]
 wg = wg.replace(old, "            px[i][2 * hf + d] = nl_pair_scalar(w, sc[2 * d], sc[2 * d + 1], sh[2 * d], sh[2 * d + 1], a.nl_slope);\n")
 wg = wg.replace("template <int TH, bool NL = false>", HELP + "template <int TH, bool NL = false>", 1)
 os.makedirs(AB, exist_ok=True)
 objs = []
-for name, text in (("conv64", c64), ("conv_wgrad", wg)):
+for name, text in (("conv64", c64), ("wgrad_ring", wg)):
     path = os.path.join(CSRC, f"_nls_{name}.hip")
     open(path, "w").write(text)
     try:
@@ -50,6 +50,6 @@ for name, text in (("conv64", c64), ("conv_wgrad", wg)):
         objs.append(o)
     finally:
         os.remove(path)
-rest = [os.path.join(OBJ, f) for f in os.listdir(OBJ) if f.endswith(".o") and f not in ("conv64.o", "conv_wgrad.o")]
+rest = [os.path.join(OBJ, f) for f in os.listdir(OBJ) if f.endswith(".o") and f not in ("conv64.o", "wgrad_ring.o")]
 subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(AB, "libmia_nlscalar.so")] + objs + rest)
 print("built tools/ab/libmia_nlscalar.so")
