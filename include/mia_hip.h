@@ -572,6 +572,27 @@ int mia_window_finalize(float* canvas, long long* pred, const float* ry, const f
  * smooth_k / 2 < h, w <= 2^20; mia_mask_denoise returns MIA_EUNSUPPORTED where mia_mask_denoise_supported returns 0. */
 int mia_mask_denoise_supported(int h, int w, int dilate, int erode, int smooth_k);
 int mia_mask_denoise(const long long* in, long long* out, int nb, int h, int w, int dilate, int erode, int smooth_k, void* stream);
+/* Connected components of int64 label maps [nvol][d][h][w] (csrc/components.hip): what `UnetProcessor.remove_cc`
+ * (models/unet/unet_processor.py:121-125, inside denoise_one_mask :72-113) only approximates with a morphological opening.  ndim 2:
+ * every [h][w] slice is an image of its own; ndim 3: every [d][h][w] volume.  Two voxels are joined when they are neighbours
+ * (connectivity 1: 4 / 6 face neighbours; connectivity == ndim: all 8 / 26) and hold the same label in [1, n_classes) -- with
+ * `foreground`, when both hold any label in that range (the reference's object mask).  A label outside [0, n_classes) belongs to no
+ * component.  roots (int32, the labels' shape) = 1 + the smallest linear index, within its image, of the voxel's component, 0
+ * elsewhere: a function of the input alone, bit-identical from run to run.  Limits: voxels per image < 2^31 - 1, 1 <= n_classes <=
+ * 256.  status: one device int32, zeroed by the call; non-zero afterwards means a union-find walk hit its iteration cap (1) or met
+ * a parent above its child (2) -- impossible unless the kernels are wrong, and then the results are not to be used. */
+int mia_cc_label(const long long* labels, int* roots, int nvol, int ndim, int d, int h, int w, int connectivity, int n_classes,
+                 int foreground, int* status, void* stream);
+/* The clean-up on those components (nnU-Net's "remove all but the largest component", which unet_processor.py:121-125 stands in
+ * for): out (int64, != labels) = fill on every voxel of a component whose exact size is < min_size, or -- with keep_largest -- which
+ * is not the winner of its (image, class), of its image with `foreground`: the largest size, ties to the lowest root (np.argmax over
+ * scipy's raster-ordered numbering).  Everything else is copied through, so kept voxels keep their class.  class_mask: HOST array of
+ * n_classes bytes read during the call, non-zero = filter that class (NULL = every class; ignored with `foreground`).  workspace:
+ * mia_cc_workspace floats, 8-byte aligned; status as for mia_cc_label. */
+int mia_cc_workspace(int nvol, int ndim, int d, int h, int w, int n_classes); /* floats; < 0 if it does not fit an int */
+int mia_cc_filter(const long long* labels, long long* out, int nvol, int ndim, int d, int h, int w, int connectivity, int n_classes,
+                  int foreground, int keep_largest, int min_size, const unsigned char* class_mask, int64_t fill, float* workspace,
+                  int* status, void* stream);
 
 #ifdef __cplusplus
 }

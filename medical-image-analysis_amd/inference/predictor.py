@@ -391,11 +391,14 @@ class EnsemblePredictor:
     signature); ``output_classes`` counts the background, and the clean-up knows labels 0 / 1 / 2 like the reference's.
     ``weights`` (one per fold, default all 1) is one extension.  ``patch_size`` is the other: with it the ensemble runs as
     ``sliding_window_predict`` (windows of that size with ``overlap``, mirrored along ``mirror_axes``, ``window_batch`` windows per
-    forward) on the preprocessed batch -- with ``image_size=None`` at the images' own resolution.  Without it nothing changes."""
+    forward) on the preprocessed batch -- with ``image_size=None`` at the images' own resolution.  Without it nothing changes.
+    ``keep_largest`` (None, "foreground", "per_class" or a tuple of classes) and ``min_component_size`` switch on the
+    connected-component clean-up of `UnetProcessor.postprocess`, applied last at the images' own size; off by default."""
 
     def __init__(self, image_size, folds: Sequence[int] = (0, 1, 2, 3, 4), in_channels: int = 3, output_classes: int = 3, device=None,
                  channels_list: Sequence[int] = DEFAULT_CHANNELS, weights: Optional[Sequence[float]] = None, patch_size=None,
-                 overlap: float = 0.5, mirror_axes: Sequence[int] = (), window_batch: int = 1, **unet_kwargs):
+                 overlap: float = 0.5, mirror_axes: Sequence[int] = (), window_batch: int = 1, keep_largest=None,
+                 min_component_size: int = 0, **unet_kwargs):
         self.folds = list(folds)
         if not self.folds:
             raise ValueError("EnsemblePredictor needs at least one fold")
@@ -405,6 +408,7 @@ class EnsemblePredictor:
             raise ValueError(f"{len(self.weights)} weights for {len(self.folds)} folds")
         self.patch_size = None if patch_size is None else ([int(patch_size)] * 2 if isinstance(patch_size, int) else [int(v) for v in patch_size])
         self.overlap, self.mirror_axes, self.window_batch = float(overlap), tuple(mirror_axes), int(window_batch)
+        self.keep_largest, self.min_component_size, self.output_classes = keep_largest, int(min_component_size), int(output_classes)
         if self.patch_size is not None:
             window_starts(self.patch_size[0], self.patch_size[0], self.overlap)  # argument errors now, not at the first image
             _mirror_combos(self.mirror_axes)
@@ -439,7 +443,8 @@ class EnsemblePredictor:
         else:
             pred = sliding_window_predict(self.models, self.preprocess(X), self.patch_size, self.overlap, self.mirror_axes, self.weights,
                                           window_batch=self.window_batch)
-        return self.processor.postprocess(pred, ori_shape, do_denoise=do_denoise)
+        return self.processor.postprocess(pred, ori_shape, do_denoise=do_denoise, keep_largest=self.keep_largest,
+                                          min_component_size=self.min_component_size, n_classes=self.output_classes)
 
     def predict(self, X, no_normalization: bool = True) -> np.ndarray:
         """One [C,H,W] image -> numpy label map [H,W] (predict.py:133-151; ``no_normalization`` is accepted and unused there too)."""

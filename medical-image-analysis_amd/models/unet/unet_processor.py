@@ -62,7 +62,14 @@ class UnetProcessor:
             image = FH.resize_bilinear(image, self.image_size[0], self.image_size[1])
         return image
 
-    def postprocess(self, P: torch.Tensor, ori_shape, do_denoise: bool = False):
+    def postprocess(self, P: torch.Tensor, ori_shape, do_denoise: bool = False, keep_largest=None, min_component_size: int = 0,
+                    n_classes=None):
+        """Nearest resize back to ``ori_shape``, the optional morphological denoise, and last -- at the original resolution -- the
+        optional connected-component clean-up (`inference.filter_components`, 4-connected): ``keep_largest`` is None (off),
+        "foreground" (keep the largest piece of the object mask), "per_class" (the largest piece of every class) or a tuple of the
+        classes to treat that way; ``min_component_size`` also drops every smaller component.  Both off: nothing changes."""
+        if not (keep_largest is None or keep_largest in ("foreground", "per_class") or isinstance(keep_largest, (tuple, list))):
+            raise ValueError(f"keep_largest={keep_largest!r}: expected None, 'foreground', 'per_class' or a tuple of classes")
         from transforms.hip import functional_hip as FH
         masks = P
         if masks.ndim == 2:
@@ -73,6 +80,11 @@ class UnetProcessor:
             masks = masks.clone()
         if do_denoise:
             masks = self.denoise_masks(masks)
+        if keep_largest is not None or min_component_size > 0:
+            from inference.components import filter_components
+            masks = filter_components(masks, keep_largest=keep_largest is not None, min_size=min_component_size,
+                                      classes=tuple(keep_largest) if isinstance(keep_largest, (tuple, list)) else None,
+                                      foreground=keep_largest == "foreground", n_classes=n_classes)
         return masks.to(P.device, dtype=P.dtype)
 
     def _denoise_binary(self, m: torch.Tensor) -> torch.Tensor:
