@@ -531,6 +531,22 @@ int mia_badge_embed(const float* logits, const void* feat, int dtype, int nb, in
 int mia_surface_distance_workspace(int nvol, int d, int h, int w, int k1); /* floats; < 0 if it does not fit an int */
 int mia_surface_distance(const long long* pred, const long long* labels, int nvol, int ndim, int d, int h, int w, int k1,
                          float sd, float sh, float sw, float* workspace, float* hd, float* asd, void* stream);
+/* The same hd / asd (bit for bit) plus the symmetric surface metrics of the same mask pairs, over the multisets
+ * S1 = {d(a, dB) : a in dA} and S2 = {d(b, dA) : b in dB} (dX = the border of mia_surface_distance), n = |dA| + |dB|:
+ *   hd_pct = numpy's linear percentile of S1 u S2 (medpy hd95 at percentile 95): pos = (double)(n - 1) * (percentile / 100.0),
+ *            k = floor(pos), v[k] + (v[min(k + 1, n - 1)] - v[k]) * (pos - k) over the ascending order v; 0 < percentile <= 100
+ *   assd   = (mean S1 + mean S2) / 2 (medpy assd; mean S1 is asd)
+ *   nsd    = (|{s in S1 : s <= tolerance[m]}| + |{s in S2 : s <= tolerance[m]}|) / n, the voxel-count surface Dice; tolerance: k1
+ *            HOST floats, finite and >= 0, in the units of the spacing; the kernels compare fp32 squared distances with tolerance^2
+ * hd_pct = assd = NaN where the prediction mask is empty, +inf where only the label mask is; nsd = 0 in both cases.  All outputs
+ * [nvol][k1] fp32.  The order statistic is exact (a radix select over the fp32 squared distances, integer atomics only): results are
+ * bit-identical from run to run and a volume's do not depend on the rest of the batch.  Arguments and limits as for
+ * mia_surface_distance, and nvol <= 4096; every check happens before any launch.
+ * Workspace: 4 floats + 1 byte per voxel + partials and select scratch: <= 5 floats per voxel + 2^22 floats, whatever k1. */
+int mia_surface_metrics_workspace(int nvol, int d, int h, int w, int k1); /* floats; < 0 outside the limits */
+int mia_surface_metrics(const long long* pred, const long long* labels, int nvol, int ndim, int d, int h, int w, int k1,
+                        float sd, float sh, float sw, double percentile, const float* tolerance, float* workspace, float* hd,
+                        float* asd, float* hd_pct, float* assd, float* nsd, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per
