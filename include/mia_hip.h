@@ -547,6 +547,35 @@ int mia_surface_metrics_workspace(int nvol, int d, int h, int w, int k1); /* flo
 int mia_surface_metrics(const long long* pred, const long long* labels, int nvol, int ndim, int d, int h, int w, int k1,
                         float sd, float sh, float sw, double percentile, const float* tolerance, float* workspace, float* hd,
                         float* asd, float* hd_pct, float* assd, float* nsd, void* stream);
+/* Signed distance maps of Kervadec et al.'s boundary loss (`one_hot2dist`; csrc/boundary.hip) for index labels [nb][h][w], int64
+ * or (label_u8 != 0) uint8, and the classes selected by bit k of class_mask (0 <= k < k1 <= 8, at least one):
+ *   phi[b][ci] = edt(~G) * ~G - (edt(G) - 1) * G,  G = (labels[b] == k), ci = the rank of k among the selected classes,
+ * edt the exact Euclidean distance transform with spacing (sh, sw) in array axis order (finite, > 0, s^2 a normal fp32); the `- 1`
+ * is literal whatever the spacing.  Pixels outside the array do not exist (an object that touches the image edge has no boundary
+ * there, scipy's rule -- the opposite of mia_surface_distance's border test).  A class that is absent from an image, or fills it,
+ * gets phi = 0 there, decided on the device.  A label outside [0, k1) is a member of no class.  phi: fp32 [nb][nc][h][w], nc = the
+ * number of selected classes; workspace: mia_sdm_workspace floats (one per phi element).  Limits: h, w <= 4096, nb * nc <= 65535,
+ * nb * nc * h * w < 2^31; every check happens before any launch.  No atomics: bit-identical from run to run, and an image's map does
+ * not depend on the rest of the batch. */
+int mia_sdm_workspace(int nb, int h, int w, int k1, int class_mask); /* floats; < 0 outside the limits */
+int mia_signed_distance_map(const void* labels, int label_u8, int nb, int h, int w, int k1, int class_mask, float sh, float sw,
+                            float* workspace, float* phi, void* stream);
+/* Boundary loss on those maps: L = (1/N) sum over images, selected classes and pixels of softmax(logits)_k * phi_k with
+ * N = nb * nc * hw.  Logits fp32 addressed by (sn, sk, sp) element strides like mia_seg_loss_fwd; phi [nb][nc][hw] as written by
+ * mia_signed_distance_map (or any fp32 map of that shape); labels are read for the range check only.  weight_dev: a DEVICE pointer
+ * to one fp32 multiplier read by the kernels at run time, or NULL for 1 -- a captured step can change it between replays.
+ * out[0] = weight * L, out[1] = L, out[2] = weight; coef: one float for the backward.  A label outside [0, k1) raises
+ * bad_label[0] / bad_label[1] exactly as mia_seg_loss_fwd: out and every gradient become NaN.  The backward writes
+ *   dlogits_j = grad_out * weight * s_j * (w_j - sum_k w_k s_k),  w_k = phi_k / N for a selected class, else 0
+ * to (gsn, gsk, gsp) strides; grad_out: device pointer to one float or NULL for 1.  Sums in double in a fixed order, no atomics:
+ * bit-identical from run to run.  slabs = blocks per image of the forward; workspace: mia_boundary_loss_workspace floats. */
+int mia_boundary_loss_workspace(int nb, int slabs); /* floats; < 0 for a bad shape */
+int mia_boundary_loss_fwd(const float* logits, const void* labels, int label_u8, const float* phi, const float* weight_dev, int nb,
+                          int64_t hw, int k1, int class_mask, int64_t sn, int64_t sk, int64_t sp, int slabs, float* workspace,
+                          float* coef, float* out, int* bad_label, void* stream);
+int mia_boundary_loss_bwd(const float* logits, const float* phi, const float* coef, const float* weight_dev, const float* grad_out,
+                          float* dlogits, int nb, int64_t hw, int k1, int class_mask, int64_t sn, int64_t sk, int64_t sp,
+                          int64_t gsn, int64_t gsk, int64_t gsp, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per

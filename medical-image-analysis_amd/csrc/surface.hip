@@ -32,7 +32,7 @@
 //   surf_sel_next_kernel      the smallest key above v[k] by integer atomicMin (skipped where v[k] occurs again after rank k)
 //   surf_finalize_ext_kernel  fp64: square roots of the two keys, the interpolation, fixed-order sums of the partials
 // Integer adds and mins commute, so these results are bit-identical from run to run and independent of the grid as well.
-#include "common.h"
+#include "edt_common.h"  // sq_dist, line_min (shared with boundary.hip)
 
 #define SURF_MAXK 8
 #define SURF_MAX_D 1024
@@ -48,25 +48,6 @@
 namespace {
 
 __device__ __forceinline__ bool in_mask(long long v, int m) { return m == 0 ? v > 0 : v == (long long)m; }
-
-__device__ __forceinline__ float sq_dist(float s, int r) {
-  const float t = s * (float)r;
-  return t * t;
-}
-
-// min_j ((s (i - j))^2 + f[j * stride]) over 0 <= j < n, scanning outward from i; f has at least one finite value
-__device__ __forceinline__ float line_min(const float* f, int stride, int n, int i, float s) {
-  float best = f[i * stride];
-  for (int r = 1;; ++r) {
-    const float dr = sq_dist(s, r);
-    if (dr >= best) break;
-    const int lo = i - r, hi = i + r;
-    if (lo < 0 && hi >= n) break;
-    if (lo >= 0) best = fminf(best, dr + f[lo * stride]);
-    if (hi < n) best = fminf(best, dr + f[hi * stride]);
-  }
-  return best;
-}
 
 struct SurfGeom {
   int nvol, d, h, w, ndim;

@@ -1438,6 +1438,102 @@ class TopKCEFn(torch.autograd.Function):
 TopKCEFn.last_threshold = None
 
 
+# ------------------------------------------------------------------ boundary loss (signed distance maps + softmax x phi)
+SDM_MAX_HW = 4096
+BOUNDARY_MAX_CLASSES = 8
+
+
+def class_mask(k1: int, classes) -> Tuple[int, Tuple[int, ...]]:
+    """(bit mask, ascending tuple) of the classes that take part; None = the foreground classes 1 .. k1-1 (Kervadec's `idc`)."""
+    if not 1 <= k1 <= BOUNDARY_MAX_CLASSES:
+        raise MiaError(f"boundary loss: {k1} classes not in [1, {BOUNDARY_MAX_CLASSES}]")
+    cls = tuple(range(1, k1)) if classes is None else tuple(sorted({int(c) for c in classes}))
+    if not cls or cls[0] < 0 or cls[-1] >= k1:
+        raise MiaError(f"boundary loss: classes {cls} must be a non-empty subset of 0..{k1 - 1}")
+    return sum(1 << c for c in cls), cls
+
+
+def _boundary_labels(labels: torch.Tensor, b: int, h: int, w: int) -> torch.Tensor:
+    """Index labels [B,H,W]: uint8 stays uint8 (one byte per pixel), anything else becomes int64."""
+    if labels.numel() != b * h * w:
+        raise MiaError(f"labels {tuple(labels.shape)} do not index {b}x{h}x{w} pixels")
+    labels = labels.reshape(b, h, w)
+    if labels.dtype != torch.uint8 and labels.dtype != torch.long:
+        labels = labels.long()
+    return labels.contiguous()
+
+
+def signed_distance_map(labels: torch.Tensor, k1: int, classes=None, spacing=None) -> torch.Tensor:
+    """phi [B, len(classes), H, W] fp32 of index labels [B,H,W] (include/mia_hip.h: mia_signed_distance_map).  No autograd, no
+    host sync, `torch.empty` only."""
+    _need_dev(labels)
+    if labels.ndim != 3:
+        raise MiaError(f"signed_distance_map: labels [B,H,W] expected, got {tuple(labels.shape)}")
+    b, h, w = labels.shape
+    mask, cls = class_mask(k1, classes)
+    sh, sw = (1.0, 1.0) if spacing is None else (float(spacing[0]), float(spacing[1]))
+    labels = _boundary_labels(labels, b, h, w)
+    words = lib().mia_sdm_workspace(b, h, w, k1, mask)
+    if words < 0:
+        raise MiaError(f"signed_distance_map: {b}x{h}x{w} with {len(cls)} classes is outside the limits (h, w <= {SDM_MAX_HW}, "
+                       f"B * classes <= 65535, B * classes * H * W < 2^31)")
+    ws = torch.empty(words, device=labels.device, dtype=torch.float32)
+    phi = torch.empty((b, len(cls), h, w), device=labels.device, dtype=torch.float32)
+    call("mia_signed_distance_map", _p(labels), int(labels.dtype == torch.uint8), b, h, w, k1, mask, _c_float(sh), _c_float(sw),
+         _p(ws), _p(phi), _stream())
+    return phi
+
+
+class BoundaryLossFn(torch.autograd.Function):
+    """weight * mean over (image, selected class, pixel) of softmax(logits)_k * phi_k: one streaming forward pass and one
+    streaming backward pass (csrc/boundary.hip).  `phi` [B, nc, H, W] fp32 carries no gradient; `weight` is None or a DEVICE
+    fp32 tensor of one element that the kernels read when they run, so a captured step follows later writes to it.  The
+    unweighted value of the latest forward stays readable as `BoundaryLossFn.last_out[1]`."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, phi, mask: int, weight):
+        _need_dev(logits, labels, phi, weight)
+        if logits.ndim != 4:
+            raise NotImplementedError("the HIP boundary loss implements 2-D inputs [B, K, H, W]")
+        logits, st = _loss_logits(logits)
+        b, k1, h, w = logits.shape
+        labels = _boundary_labels(labels, b, h, w)
+        nc = bin(mask).count("1")
+        if tuple(phi.shape) != (b, nc, h, w) or phi.dtype != torch.float32:
+            raise MiaError(f"boundary loss: distance map {tuple(phi.shape)} {phi.dtype}, expected fp32 {(b, nc, h, w)}")
+        phi = phi.detach().contiguous()
+        if weight is not None:
+            if weight.dtype != torch.float32 or weight.numel() != 1:
+                raise MiaError("boundary loss: `weight` is one fp32 value on the device")
+            weight = weight.detach()
+        hw = h * w
+        slabs = _loss_slabs(hw)
+        dev = logits.device
+        ws = torch.empty(lib().mia_boundary_loss_workspace(b, slabs), device=dev, dtype=torch.float32)
+        coef = torch.empty(1, device=dev, dtype=torch.float32)  # written by the finalize kernel
+        out = torch.empty(3, device=dev, dtype=torch.float32)
+        bad = _bad_flags(dev)
+        call("mia_boundary_loss_fwd", _p(logits), _p(labels), int(labels.dtype == torch.uint8), _p(phi), _p(weight), b, _c_i64(hw), k1,
+             mask, *_strides_i64(st), slabs, _p(ws), _p(coef), _p(out), _p(bad), _stream())
+        ctx.save_for_backward(logits, phi, coef)
+        ctx.weight = weight
+        ctx.mask, ctx.st = mask, st
+        BoundaryLossFn.last_out = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, phi, coef = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl, gst, g = _loss_bwd_begin(logits, gout)
+        call("mia_boundary_loss_bwd", _p(logits), _p(phi), _p(coef), _p(ctx.weight), _p(g), _p(dl), b, _c_i64(h * w), k1, ctx.mask,
+             *_strides_i64(ctx.st), *_strides_i64(gst), _stream())
+        return dl, None, None, None, None
+
+
+BoundaryLossFn.last_out = None
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 
