@@ -576,6 +576,40 @@ int mia_boundary_loss_fwd(const float* logits, const void* labels, int label_u8,
 int mia_boundary_loss_bwd(const float* logits, const float* phi, const float* coef, const float* weight_dev, const float* grad_out,
                           float* dlogits, int nb, int64_t hw, int k1, int class_mask, int64_t sn, int64_t sk, int64_t sp,
                           int64_t gsn, int64_t gsk, int64_t gsp, void* stream);
+/* Mean-teacher consistency (csrc/consistency.hip; Tarvainen & Valpola 2017, UA-MT of Yu et al. 2019; the reference has no such
+ * code): softmax-MSE between student logits zs and teacher logits zt, both fp32, each addressed by its own (sn, sk, sp) /
+ * (tsn, tsk, tsp) element strides like mia_seg_loss_fwd (the layouts may differ; a batch slice of a larger tensor works), 1 <= k1 <= 8.
+ * With ps = softmax(zs), pt = softmax(zt), e_k = ps_k - pt_k, d = sum_k e_k^2 per pixel:
+ *   prob_mean == NULL (plain):  L = sum d / (nb * k1 * hw)  -- torch.mean((ps - pt)**2)
+ *   prob_mean != NULL (masked): prob_mean planar fp32 [nb][k1][hw] (what mia_softmax_accum leaves after T passes of weight 1/T),
+ *     u = -sum_k prob_mean_k * log(prob_mean_k + 1e-6), keep = (u < threshold), n_keep = sum keep,
+ *     L = sum keep * d / (den_scale * n_keep + 1e-16);  n_keep == 0 gives L = 0 and a zero gradient, not NaN
+ * dyn_dev: DEVICE array {weight, threshold} of two fp32 values read by the kernels at run time (a captured step follows later
+ * writes), or NULL for weight 1 -- the plain form only: prob_mean needs dyn_dev.  out[0] = weight * L, out[1] = L, out[2] = weight;
+ * n_keep[0] = the kept pixels as an exact integer (nb * hw in the plain form); keep: byte map [nb][hw] (1 = kept) that the backward
+ * reads, so both directions agree on every pixel and the backward does not read prob_mean (may be NULL in the plain form); coef[0] =
+ * 1 / denominator.  The backward writes
+ *   dzs_j = grad_out * weight * coef * keep * 2 * ps_j * (e_j - sum_k ps_k e_k)
+ * to (gsn, gsk, gsp) strides (grad_out: device pointer to one float or NULL for 1; keep NULL = every pixel); zt and prob_mean get no
+ * gradient.  Block partials, then one finalize block in double / int64, in a fixed order, no atomics: bit-identical from run to run,
+ * and an image's keep map does not depend on the rest of the batch.  Four pixels per thread with 16-byte accesses for planar
+ * (sp == 1) and channels-last (sk == 1, sp == k1) tensors when hw % 4 == 0 and pointers / strides are 16-byte aligned (the rule of
+ * mia_softmax_accum; the gradient must then have the student's layout class), one pixel per thread otherwise.  slabs = blocks per
+ * image of the forward; workspace: mia_consistency_workspace 4-byte words.  Limits: nb * hw < 2^31.  Every check happens before any
+ * launch. */
+int mia_consistency_workspace(int nb, int slabs); /* 4-byte words; < 0 for a bad shape */
+int mia_consistency_fwd(const float* zs, const float* zt, const float* prob_mean, const float* dyn_dev, int nb, int64_t hw, int k1,
+                        int64_t sn, int64_t sk, int64_t sp, int64_t tsn, int64_t tsk, int64_t tsp, float den_scale, int slabs,
+                        float* workspace, unsigned char* keep, float* coef, float* out, long long* n_keep, void* stream);
+int mia_consistency_bwd(const float* zs, const float* zt, const unsigned char* keep, const float* coef, const float* dyn_dev,
+                        const float* grad_out, float* dzs, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
+                        int64_t tsn, int64_t tsk, int64_t tsp, int64_t gsn, int64_t gsk, int64_t gsp, void* stream);
+/* teacher[i] = alpha * teacher[i] + (1 - alpha) * student[i] over n fp32 values (the mean teacher's exponential moving average over
+ * FlatOptimizer.flat_param), evaluated in double and rounded once.  alpha_dev: DEVICE pointer to one float read at run time, or
+ * NULL to use the host value `alpha` (then 0 <= alpha <= 1).  alpha == 0 copies the student bit for bit.  16-byte accesses where
+ * both buffers are 16-byte aligned at the same element, one element at a time for the head, the tail and differently aligned
+ * buffers; both must be 4-byte aligned and must not overlap. */
+int mia_ema_update(float* teacher, const float* student, int64_t n, float alpha, const float* alpha_dev, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per

@@ -1534,6 +1534,94 @@ class BoundaryLossFn(torch.autograd.Function):
 BoundaryLossFn.last_out = None
 
 
+# ------------------------------------------------------------------ mean-teacher consistency (softmax MSE, uncertainty mask, EMA)
+CONSISTENCY_MAX_CLASSES = 8
+
+
+def _consistency_slabs(hw: int) -> int:
+    """Blocks per image of the consistency forward: one per 2048 pixels (two four-pixel groups per thread), at most 1024.  Finer than
+    `_loss_slabs`: the forward evaluates two soft-maxes in double per pixel, and the unlabelled half of a batch is few images."""
+    return max(1, min(1024, hw // 2048))
+
+
+class ConsistencyFn(torch.autograd.Function):
+    """weight * softmax-MSE between student and teacher logits [B, K, H, W], optionally masked by the entropy of `prob_mean`
+    (include/mia_hip.h: mia_consistency_fwd; csrc/consistency.hip): one streaming forward pass and one streaming backward pass.
+    Only the student's logits get a gradient.  `dyn` is None or a DEVICE fp32 tensor {weight, threshold} that the kernels read when
+    they run, so a captured step follows later writes to it; `prob_mean` (contiguous fp32 [B, K, H, W]) needs it.  By-products of
+    the latest forward, all on the device: `last_out` = {weight * L, L, weight}, `last_kept` (int64, one element), `last_keep` (the
+    byte map [B, H, W], None in the plain form)."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, prob_mean, dyn, den_scale: float):
+        _need_dev(student, teacher, prob_mean, dyn)
+        if student.ndim != 4:
+            raise NotImplementedError("the HIP consistency loss implements 2-D inputs [B, K, H, W]")
+        if teacher.shape != student.shape:
+            raise MiaError(f"consistency loss: teacher logits {tuple(teacher.shape)} and student logits {tuple(student.shape)} differ")
+        student, st = _loss_logits(student)
+        teacher, tt = _loss_logits(teacher.detach())
+        b, k1, h, w = student.shape
+        if dyn is not None:
+            if dyn.dtype != torch.float32 or dyn.numel() != 2 or not dyn.is_contiguous():
+                raise MiaError("consistency loss: `dyn` is two contiguous fp32 values {weight, threshold} on the device")
+            dyn = dyn.detach()
+        hw = h * w
+        dev = student.device
+        keep = None
+        if prob_mean is not None:
+            if tuple(prob_mean.shape) != (b, k1, h, w) or prob_mean.dtype != torch.float32:
+                raise MiaError(f"consistency loss: prob_mean {tuple(prob_mean.shape)} {prob_mean.dtype}, expected fp32 {(b, k1, h, w)}")
+            if dyn is None:
+                raise MiaError("consistency loss: prob_mean needs `dyn` (the threshold is read from dyn[1])")
+            prob_mean = prob_mean.detach().contiguous()
+            if b > 0 and hw > 0:
+                keep = torch.empty((b, h, w), device=dev, dtype=torch.uint8)  # every byte is written by the forward kernel
+        slabs = _consistency_slabs(hw)
+        words = max(lib().mia_consistency_workspace(b, slabs), 0)  # < 0: a bad shape, reported by the call below
+        buf = torch.empty(words + 4, device=dev, dtype=torch.float32)  # workspace | out[3] | coef: one allocation, every word written
+        ws, out, coef = buf[:words], buf[words:words + 3], buf[words + 3:]
+        kept = torch.empty(1, device=dev, dtype=torch.int64)
+        call("mia_consistency_fwd", _p(student), _p(teacher), _p(prob_mean), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(st),
+             *_strides_i64(tt), _c_float(den_scale), slabs, _p(ws), _p(keep), _p(coef), _p(out), _p(kept), _stream())
+        ctx.save_for_backward(student, teacher, coef)
+        ctx.keep, ctx.dyn, ctx.st, ctx.tt = keep, dyn, st, tt
+        ConsistencyFn.last_out, ConsistencyFn.last_kept, ConsistencyFn.last_keep = out, kept, keep
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        student, teacher, coef = ctx.saved_tensors
+        b, k1, h, w = student.shape
+        dl, gst, g = _loss_bwd_begin(student, gout)
+        call("mia_consistency_bwd", _p(student), _p(teacher), _p(ctx.keep), _p(coef), _p(ctx.dyn), _p(g), _p(dl), b, _c_i64(h * w), k1,
+             *_strides_i64(ctx.st), *_strides_i64(ctx.tt), *_strides_i64(gst), _stream())
+        return dl, None, None, None, None
+
+
+ConsistencyFn.last_out = ConsistencyFn.last_kept = ConsistencyFn.last_keep = None
+
+
+def ema_update(teacher_flat: torch.Tensor, student_flat: torch.Tensor, alpha) -> None:
+    """teacher_flat = alpha * teacher_flat + (1 - alpha) * student_flat in place over flat fp32 buffers (include/mia_hip.h:
+    mia_ema_update); `alpha` is a float in [0, 1] or a DEVICE fp32 tensor of one element read when the kernel runs.  alpha == 0
+    copies the student bit for bit.  The kernel bypasses tensor version counters: the caller bumps the parameter epoch (or re-packs)
+    when the buffer backs a model's parameters."""
+    _need_dev(teacher_flat, student_flat)
+    for t in (teacher_flat, student_flat):
+        if t.dtype != torch.float32 or t.ndim != 1 or not t.is_contiguous():
+            raise MiaError("ema_update: flat contiguous fp32 buffers expected")
+    if teacher_flat.numel() != student_flat.numel():
+        raise MiaError(f"ema_update: {teacher_flat.numel()} teacher values against {student_flat.numel()} student values")
+    adev = None
+    if isinstance(alpha, torch.Tensor):
+        _need_dev(alpha)
+        if alpha.dtype != torch.float32 or alpha.numel() != 1:
+            raise MiaError("ema_update: a device `alpha` is one fp32 value")
+        adev, alpha = alpha, 0.0
+    call("mia_ema_update", _p(teacher_flat), _p(student_flat), _c_i64(teacher_flat.numel()), _c_float(float(alpha)), _p(adev), _stream())
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 

@@ -1,0 +1,247 @@
+"""Mean-teacher semi-supervised train step (Tarvainen & Valpola 2017; UA-MT: Yu et al., MICCAI 2019) for the MI355X UNet path.
+
+The reference's `SemiTrainer` is a supervised loop; this is the project's own addition.  A batch holds `labeled_bs` labelled
+images followed by unlabelled ones.  The student is trained with `supervised_loss` on the labelled part plus a softmax-MSE
+consistency term (`losses.consistency_loss.SoftmaxMSEConsistency`, csrc/consistency.hip) that pulls its logits on the unlabelled
+part towards those of a teacher -- a second network of the same architecture whose weights are the exponential moving average of
+the student's (`ops.ema_update`: ONE pass over `FlatOptimizer.flat_param`).  With `uncertainty_passes = T > 0` the term is masked
+by the entropy of the mean of T stochastic teacher passes (fresh input noise, fresh Dropout2d masks), accumulated by the
+prediction path's `mia_softmax_accum`.
+
+`MeanTeacherEngine` composes `FlatOptimizer`, `PolyLRScheduler` and the loss modules; `TrainEngine` is not involved.
+
+Out of scope:
+* hipGraph capture of this step: it runs eagerly.  The consistency weight and the entropy threshold already live in a device
+  buffer (`dyn`) that the kernels read when they run, so a capture can follow later.
+* more than one rank: the constructor raises `NotImplementedError`.
+* 3-D inputs, deep supervision.
+"""
+from __future__ import annotations
+
+import math
+from pathlib import Path
+from typing import Optional
+
+import torch
+import torch.distributed as dist
+
+from mia_hip import ops
+from scheduler.lr_scheduler import PolyLRScheduler
+from training.engine import FlatOptimizer
+
+TEACHER_FILE = "mean_teacher.pth"
+
+
+def ema_alpha(step: int, ema_decay: float) -> float:
+    """The published schedule: `min(1 - 1 / (step + 1), ema_decay)` with `step` the number of EMA updates done so far -- the first
+    update copies the student (alpha = 0), the early ones average quickly, later ones use `ema_decay`."""
+    return min(1.0 - 1.0 / (step + 1), float(ema_decay))
+
+
+def entropy_threshold(ramp: float, num_classes: int) -> float:
+    """UA-MT's threshold `(0.75 + 0.25 * ramp) * ln(K)` for K classes (background included) and a ramp value in [0, 1]."""
+    return (0.75 + 0.25 * float(ramp)) * math.log(num_classes)
+
+
+def _ramp_value(r, i: int) -> float:
+    """A float, or any object with `.step(i)` (the reference's `scheduler.ramps.BaseRampUp` protocol)."""
+    return float(r.step(i)) if hasattr(r, "step") else float(r)
+
+
+class MeanTeacherEngine:
+    """student + EMA teacher + supervised loss + consistency loss + flat optimizer + poly LR.  `train_step` returns the loss TENSOR
+    (no host sync); `last_supervised`, `last_consistency` (unweighted) and `last_kept` are device by-products of the latest step.
+
+    teacher: a second `UNet` of the student's architecture.  Its trainable parameters become views into `teacher_flat`, a buffer
+    with the student's `FlatOptimizer` offsets, initialised bit for bit from the student; they never receive a gradient.  The teacher
+    stays in train mode during training (its Dropout2d masks are what makes the uncertainty passes stochastic, as in the published
+    code).
+    consistency: None = `SoftmaxMSEConsistency` for the student's classes; a module with that call signature; False = no teacher
+    pass and no consistency term (the EMA still runs).
+    consistency_weight, threshold_ramp: a float or an object with `.step(i)`; each step the engine writes
+    `weight_i` and `threshold_i = (0.75 + 0.25 * ramp_i) * ln(K)` into the device buffer `dyn` before anything reads it, outside
+    the autograd graph.  threshold_ramp None = 0, i.e. the schedule's strictest threshold `0.75 ln K` throughout.
+    uncertainty_passes: T extra teacher passes whose mean soft-max masks the consistency term; 0 = the plain Mean Teacher form.
+    noise_std, noise_clip: the teacher sees `image + clamp(N(0, noise_std^2), -noise_clip, noise_clip)`."""
+
+    def __init__(self, model, teacher, supervised_loss, labeled_bs: int, ema_decay: float = 0.99, consistency=None,
+                 consistency_weight=0.1, uncertainty_passes: int = 0, threshold_ramp=None, noise_std: float = 0.1,
+                 noise_clip: float = 0.2, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
+                 start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
+                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
+            raise NotImplementedError("MeanTeacherEngine runs on one rank (the EMA and the teacher passes are not sharded yet)")
+        if labeled_bs < 1:
+            raise ValueError("MeanTeacherEngine: labeled_bs must be at least 1")
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("MeanTeacherEngine: ema_decay must lie in [0, 1]")
+        if uncertainty_passes < 0:
+            raise ValueError("MeanTeacherEngine: uncertainty_passes must not be negative")
+        self.model, self.teacher = model, teacher
+        self.supervised_loss = supervised_loss
+        self.labeled_bs = int(labeled_bs)
+        self.ema_decay = float(ema_decay)
+        self.uncertainty_passes = int(uncertainty_passes)
+        self.consistency_weight, self.threshold_ramp = consistency_weight, threshold_ramp
+        self.noise_std, self.noise_clip = float(noise_std), float(noise_clip)
+        self.optimizer = FlatOptimizer(model, optimizer_name, **dict(optimizer_kwargs or {}))
+        if lr_scheduler_name == "poly":
+            self.lr_scheduler = PolyLRScheduler(self.optimizer, initial_lr=start_lr, max_steps=num_iters,
+                                                warmup_steps=lr_warmup_iter, interval=lr_interval)
+        elif lr_scheduler_name == "none":
+            self.lr_scheduler = None
+        else:
+            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
+        self.grad_norm = grad_norm
+        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
+        if consistency is None:
+            from losses.consistency_loss import SoftmaxMSEConsistency
+            consistency = SoftmaxMSEConsistency(self.num_classes - 1)
+        self.consistency = consistency or None
+        self._adopt_teacher()
+        dev = self.optimizer.flat_param.device
+        self.dyn = torch.zeros(2, device=dev, dtype=torch.float32)  # {weight, threshold}, read by the kernels when they run
+        self.current_iter = 0
+        self.ema_step = 0
+        self._teacher_plan = None
+        self._one = None
+        self.last_supervised = self.last_consistency = self.last_kept = None
+
+    def _adopt_teacher(self) -> None:
+        """Teacher parameters -> views into `teacher_flat` at the student's offsets; values and buffers copied from the student."""
+        opt = self.optimizer
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        tparams = dict(self.teacher.named_parameters())
+        if set(tparams) != set(names.values()) or any(tparams[names[id(p)]].shape != p.shape for p in opt.params):
+            raise ValueError("MeanTeacherEngine: the teacher must have the student's architecture (same parameter names and shapes)")
+        self.teacher.to(opt.flat_param.device)
+        self.teacher.load_state_dict(self.model.state_dict())  # buffers and frozen parameters; the trainable ones again below
+        self.teacher_flat = torch.zeros_like(opt.flat_param)
+        self.teacher_params = []
+        with torch.no_grad():
+            self.teacher_flat.copy_(opt.flat_param)
+            for p, o in zip(opt.params, opt.offsets):
+                t = tparams[names[id(p)]]
+                t.data = self.teacher_flat[o:o + p.numel()].view(p.shape)
+                t.requires_grad_(False)
+                t.grad = None
+                self.teacher_params.append(t)
+        for t in self.teacher.parameters():
+            t.requires_grad_(False)
+        ops.bump_param_epoch()
+
+    def _write_dyn(self) -> None:
+        w = _ramp_value(self.consistency_weight, self.current_iter)
+        r = 0.0 if self.threshold_ramp is None else _ramp_value(self.threshold_ramp, self.current_iter)
+        self.dyn[0].fill_(w)  # two fill launches that carry the values as arguments: no staging copy, no host sync
+        self.dyn[1].fill_(entropy_threshold(r, self.num_classes))
+
+    def _noisy(self, x: torch.Tensor) -> torch.Tensor:
+        if self.noise_std == 0.0:
+            return x
+        return x + torch.clamp(torch.randn_like(x) * self.noise_std, -self.noise_clip, self.noise_clip)
+
+    @torch.no_grad()
+    def _teacher_passes(self, unlabeled: torch.Tensor):
+        """(zt, pbar): the teacher's logits on one noisy copy, and the mean soft-max of `uncertainty_passes` further stochastic passes
+        (None without them).  Runs BEFORE the student's forward: `UNet.forward` clears the producer -> consumer hints that belong to
+        the backward of the latest forward."""
+        zt = self.teacher(self._noisy(unlabeled))
+        pbar = None
+        if self.uncertainty_passes > 0:
+            from inference.predictor import softmax_accum
+            pbar = torch.empty(zt.shape, device=zt.device, dtype=torch.float32)
+            for i in range(self.uncertainty_passes):
+                softmax_accum(self.teacher(self._noisy(unlabeled)), pbar, None, weight=1.0 / self.uncertainty_passes, first=i == 0)
+        return zt, pbar
+
+    def train_step(self, sampled_batch) -> torch.Tensor:
+        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
+        self.model.train()
+        self.teacher.train()
+        if self.lr_scheduler:
+            self.lr_scheduler.step(self.current_iter)
+        dev = self.optimizer.flat_param.device
+        lb = self.labeled_bs
+        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
+        label = sampled_batch["label"].to(dev, non_blocking=True)
+        if image.ndim != 4:
+            raise NotImplementedError("MeanTeacherEngine implements 2-D inputs [B, C, H, W]")
+        if label.shape[0] < lb or image.shape[0] < lb:
+            raise ValueError(f"MeanTeacherEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
+        consistent = self.consistency is not None and image.shape[0] > lb
+        if consistent:
+            self._write_dyn()
+            zt, pbar = self._teacher_passes(image[lb:])
+        output = self.model(image)
+        sup = self.supervised_loss(output[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        if consistent:
+            loss = sup + self.consistency(output[lb:], zt, pbar, dyn=self.dyn)
+            self.last_consistency = getattr(self.consistency, "last_value", None)
+            self.last_kept = getattr(self.consistency, "last_kept", None)
+        else:
+            loss = sup
+        self.optimizer.zero_grad()
+        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+            self._one = torch.ones_like(loss)
+        loss.backward(self._one)
+        self.optimizer.step(max_grad_norm=self.grad_norm)
+        self.current_iter += 1
+        self._update_teacher()
+        return loss.detach()
+
+    def _ema(self, alpha: float) -> None:
+        ops.ema_update(self.teacher_flat, self.optimizer.flat_param, alpha)
+
+    def _update_teacher(self) -> None:
+        """The EMA over the flat buffers, then the teacher's packed weight copies.  The optimizer step just before has moved the
+        parameter epoch on, so every packed copy of a teacher weight made before this point misses on its next use; the plan
+        re-packs them in one launch and marks them current."""
+        self._ema(ema_alpha(self.ema_step, self.ema_decay))
+        self.ema_step += 1
+        if self.ema_step < 2 or not self.teacher_flat.is_cuda:
+            return
+        if self._teacher_plan is None or not self._teacher_plan.valid():
+            dts = set()
+            for t in self.teacher_params:
+                c = ops._caches.get(id(t))
+                if c is not None and c[0]() is t:
+                    dts.update(dt for dt, _ in c[1]._store)
+            if len(dts) != 1:  # nothing packed yet (no teacher pass so far), or mixed compute dtypes: the per-tensor path
+                return
+            self._teacher_plan = ops.PackPlan(self.teacher_params, dts.pop())
+        self._teacher_plan.repack()
+
+    def loss_value(self, loss: torch.Tensor) -> float:
+        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
+        v = float(loss.item())
+        ops.check_labels()
+        return v
+
+    @torch.no_grad()
+    def predict(self, image: torch.Tensor, use_teacher: bool = False) -> torch.Tensor:
+        """eval forward -> softmax -> argmax, with the student's or the teacher's weights."""
+        net = self.teacher if use_teacher else self.model
+        net.eval()
+        out = net(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
+        return out.softmax(1).argmax(1)
+
+    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
+        """The student as `TrainEngine.save_state_dict` writes it (model.pth, training_state.pth on request: the reference's
+        layout), plus the teacher's `state_dict` and the EMA step count in a file of their own."""
+        from training import checkpoint
+        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+        torch.save({"teacher": checkpoint.model_state_for_save(self.teacher), "ema_step": int(self.ema_step)},
+                   Path(save_path) / TEACHER_FILE)
+
+    def load_state_dict(self, save_path) -> dict:
+        from training import checkpoint
+        out = checkpoint.load_state_dict(self, save_path)
+        tf = Path(save_path) / TEACHER_FILE
+        if tf.is_file():
+            sd = torch.load(tf, map_location=self.teacher_flat.device, weights_only=True)
+            self.teacher.load_state_dict(sd["teacher"])  # copy_ into the flat-buffer views
+            self.ema_step = int(sd["ema_step"])
+        ops.bump_param_epoch()  # packed weights of both networks are stale now
+        return out
