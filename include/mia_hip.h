@@ -610,6 +610,29 @@ int mia_consistency_bwd(const float* zs, const float* zt, const unsigned char* k
  * both buffers are 16-byte aligned at the same element, one element at a time for the head, the tail and differently aligned
  * buffers; both must be 4-byte aligned and must not overlap. */
 int mia_ema_update(float* teacher, const float* student, int64_t n, float alpha, const float* alpha_dev, void* stream);
+/* Uncertainty rectified pyramid consistency (csrc/urpc.hip; URPC: Luo et al., MICCAI 2021 / MedIA 2022; the reference has no such
+ * code) between the ns outputs one network makes at several decoder scales, on unlabelled images.  z, factors, strides (and dz,
+ * gstrides) are HOST arrays of ns entries, read during the call: z[s] = DEVICE pointer to fp32 logits [nb][k1][(H / f_s) * (W / f_s)]
+ * addressed by strides[3 s ..] = (sn, sk, sp) in elements like mia_ds_loss_fwd (planar, channels-last, padded, a batch slice; sk and
+ * sp below 2^31); factors[0] = 1 (the full-resolution output), every other factor one of 2, 4, 8, 16 (any order) and a divisor of H
+ * and W; 2 <= ns <= 5, 1 <= k1 <= 8, nb * H * W < 2^31.  Per full-resolution pixel, P = nb * H * W:
+ *   u_s = up(z_s) (torch interpolate(scale_factor=f_s, mode="bilinear", align_corners=False), in registers; identity for f_s = 1)
+ *   p_s = softmax(u_s), lp_s = u_s - logsumexp(u_s), m = (1/ns) sum_s p_s
+ *   v_s = sum_k m_k (log m_k - lp_sk)  (a class with m_k == 0 adds 0),  w_s = exp(-v_s),  D_s = sum_k (m_k - p_sk)^2
+ *   sums[s] = (sum D_s w_s, sum w_s, sum v_s) over all pixels;  terms[s] = L_s = (sums[s][0] / (P k1)) / (sums[s][1] / P + 1e-8)
+ *   + sums[s][2] / P;  L = (1/ns) sum_s L_s;  out[0] = weight * L, out[1] = L, weight = dyn_dev[0] read on the device when the
+ *   finalize kernel runs (dyn_dev NULL: 1).
+ * The backward recomputes everything from the logits and `sums` (nothing of full-resolution size is kept) and writes, for every
+ * scale, dz[s] = grad_out * weight * dL/dz_s through gstrides[3 s ..]: plain autograd of the expression above, the mean m
+ * included (grad_out: device pointer to one float or NULL for 1).  The full-resolution scale takes one streaming pass, every other
+ * one launch of the gather mia_ds_loss_bwd uses.  No float atomics, every sum in a fixed order: out, sums, terms and every dz are
+ * bit-identical run to run; no host sync.  slabs = blocks per image of the forward; workspace: mia_urpc_workspace floats.  Every
+ * check happens before any launch. */
+int mia_urpc_workspace(int nb, int ns, int slabs); /* floats; < 0 for a bad shape */
+int mia_urpc_fwd(const float* const* z, const int* factors, const int64_t* strides, int ns, int nb, int H, int W, int k1,
+                 const float* dyn_dev, int slabs, float* workspace, float* sums, float* terms, float* out, void* stream);
+int mia_urpc_bwd(const float* const* z, const int* factors, const int64_t* strides, float* const* dz, const int64_t* gstrides, int ns,
+                 int nb, int H, int W, int k1, const float* sums, const float* dyn_dev, const float* grad_out, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per

@@ -1622,6 +1622,82 @@ def ema_update(teacher_flat: torch.Tensor, student_flat: torch.Tensor, alpha) ->
     call("mia_ema_update", _p(teacher_flat), _p(student_flat), _c_i64(teacher_flat.numel()), _c_float(float(alpha)), _p(adev), _stream())
 
 
+# ------------------------------------------------------------------ pyramid consistency (URPC) between a network's own scales
+URPC_MAX_SCALES = 5
+
+
+def _urpc_slabs(hw: int) -> int:
+    """Blocks per image of the pyramid-consistency forward: one per 2048 pixels, at most 256 (a pixel costs S soft-maxes and the
+    unlabelled part of a batch is few images)."""
+    return max(1, min(256, hw // 2048))
+
+
+def _host_arrays(tensors, strides):
+    """(device pointers, (sn, sk, sp) triples) as the host arrays the URPC entry points read during the call."""
+    n = len(tensors)
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+    return ptrs, (ctypes.c_int64 * (3 * n))(*[int(v) for st in strides for v in st])
+
+
+class PyramidConsistencyFn(torch.autograd.Function):
+    """`apply(dyn, *logits)` -> weight * L, the uncertainty rectified pyramid consistency (URPC) between the S = len(logits) outputs
+    one network makes at several scales (include/mia_hip.h: mia_urpc_fwd; csrc/urpc.hip).  logits[0] is the full-resolution output
+    [B, K, H, W]; every other entry is [B, K, H / f, W / f] with f in `DS_LOSS_FACTORS`, in any order; fp32, any layout whose H and W
+    collapse (planar, the head's channels-last view, a batch slice of either).  Every entry gets a gradient.  `dyn` is None (weight
+    1) or a DEVICE fp32 tensor whose first element is the weight, read when the kernels run.  By-products of the latest forward, on the
+    device: `last_out` = {weight * L, L} and `last_terms` [S] (the per-scale L_s).  Nothing of full-resolution size is allocated in
+    either direction."""
+
+    @staticmethod
+    def forward(ctx, dyn, *logits):
+        _need_dev(dyn, *logits)
+        ns = len(logits)
+        if not 2 <= ns <= URPC_MAX_SCALES:
+            raise MiaError(f"pyramid consistency: {ns} outputs, the kernel takes 2 to {URPC_MAX_SCALES}")
+        if any(z.ndim != 4 for z in logits):
+            raise NotImplementedError("the HIP pyramid consistency implements 2-D inputs [B, K, H, W]")
+        b, k1, hh, ww = logits[0].shape
+        factors = []
+        for z in logits:
+            if z.shape[0] != b or z.shape[1] != k1 or hh % z.shape[2] or ww % z.shape[3] or hh // z.shape[2] != ww // z.shape[3]:
+                raise MiaError(f"pyramid consistency: output {tuple(z.shape)} against the full-resolution {tuple(logits[0].shape)}")
+            factors.append(hh // z.shape[2])
+        if dyn is not None:
+            if dyn.dtype != torch.float32 or dyn.numel() < 1 or not dyn.is_contiguous():
+                raise MiaError("pyramid consistency: `dyn` is a contiguous fp32 device tensor whose first element is the weight")
+            dyn = dyn.detach()
+        zs, sts = zip(*[_loss_logits(z) for z in logits])
+        dev = zs[0].device
+        slabs = _urpc_slabs(hh * ww)
+        words = max(lib().mia_urpc_workspace(b, ns, slabs), 0)  # < 0: a bad shape, reported by the call below
+        buf = torch.empty(words + 4 * ns + 2, device=dev, dtype=torch.float32)  # workspace | sums | terms | out: every word written
+        ws, sums = buf[:words], buf[words:words + 3 * ns]
+        terms, out = buf[words + 3 * ns:words + 4 * ns], buf[words + 4 * ns:]
+        zp, zst = _host_arrays(zs, sts)
+        fac = (ctypes.c_int * ns)(*factors)
+        call("mia_urpc_fwd", zp, fac, zst, ns, b, hh, ww, k1, _p(dyn), slabs, _p(ws), _p(sums), _p(terms), _p(out), _stream())
+        ctx.save_for_backward(sums, *zs)
+        ctx.dyn, ctx.factors, ctx.sts = dyn, factors, sts
+        PyramidConsistencyFn.last_out, PyramidConsistencyFn.last_terms = out, terms
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        sums, *zs = ctx.saved_tensors
+        ns = len(zs)
+        b, k1, hh, ww = zs[0].shape
+        dzs = [torch.empty_like(z) for z in zs]
+        g = gout.reshape(1).float().contiguous()
+        zp, zst = _host_arrays(zs, ctx.sts)
+        dp, dst = _host_arrays(dzs, [_pix_strides(d) for d in dzs])
+        fac = (ctypes.c_int * ns)(*ctx.factors)
+        call("mia_urpc_bwd", zp, fac, zst, dp, dst, ns, b, hh, ww, k1, _p(sums), _p(ctx.dyn), _p(g), _stream())
+        return (None, *dzs)
+
+
+PyramidConsistencyFn.last_out = PyramidConsistencyFn.last_terms = None
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 

@@ -14,7 +14,12 @@ Out of scope:
 * hipGraph capture of this step: it runs eagerly.  The consistency weight and the entropy threshold already live in a device
   buffer (`dyn`) that the kernels read when they run, so a capture can follow later.
 * more than one rank: the constructor raises `NotImplementedError`.
-* 3-D inputs, deep supervision.
+* 3-D inputs; deep supervision in `MeanTeacherEngine` (the one-network case is `URPCEngine` below).
+
+`URPCEngine` is the one-network method of the same tables (URPC: Luo et al., MICCAI 2021 / MedIA 2022): no teacher and no extra
+passes.  The network's own multi-scale outputs (`UNet(deep_supervision=True, ds_layer=n)`) are all supervised on the labelled images
+and asked to agree on the unlabelled ones (`losses.pyramid_consistency.PyramidConsistencyLoss`, csrc/urpc.hip).  Same batch
+convention, same device-resident schedule buffer `dyn`; it runs eagerly on one rank on 2-D inputs, with index labels.
 """
 from __future__ import annotations
 
@@ -245,3 +250,109 @@ class MeanTeacherEngine:
             self.ema_step = int(sd["ema_step"])
         ops.bump_param_epoch()  # packed weights of both networks are stale now
         return out
+
+
+class URPCEngine:
+    """one network + deep-supervised loss on the labelled images + pyramid consistency on the unlabelled ones + flat optimizer + poly
+    LR.  `train_step` returns the loss TENSOR (no host sync); `last_supervised` and `last_consistency` (unweighted) are device
+    by-products of the latest step.
+
+    model: a `UNet` built with auxiliary heads (`deep_supervision=True, ds_layer >= 2`).  Per step
+        outs = model(image, return_ds=True, upsample_ds=False)
+        sup  = DeepSupervisionLoss(supervised_loss, weights=[1/S] * S)([o[:labeled_bs] for o in outs], label[:labeled_bs])
+        cons = consistency([o[labeled_bs:] for o in outs], dyn=dyn)           skipped when the batch has no unlabelled image
+    consistency: None = `PyramidConsistencyLoss()`; a module with that call signature; False = no consistency term.
+    consistency_weight: a float or an object with `.step(i)`; each step the engine writes `weight_i` into the device buffer `dyn`
+    before anything reads it, outside the autograd graph."""
+
+    def __init__(self, model, supervised_loss, labeled_bs: int, consistency=None, consistency_weight=0.1,
+                 optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000,
+                 lr_warmup_iter: int = 250, lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0,
+                 process_group=None):
+        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
+            raise NotImplementedError("URPCEngine runs on one rank")
+        if labeled_bs < 1:
+            raise ValueError("URPCEngine: labeled_bs must be at least 1")
+        heads = getattr(getattr(model, "decoder", None), "ds", None)
+        if heads is None or all(h is None for h in heads):
+            raise ValueError("URPCEngine needs a model whose decoder has auxiliary heads (UNet(deep_supervision=True, ds_layer >= 2)): "
+                             "the consistency term compares their outputs")
+        self.model = model
+        self.num_outputs = 1 + sum(h is not None for h in heads)
+        from losses.deep_supervision import DeepSupervisionLoss
+        self.supervised_loss = DeepSupervisionLoss(supervised_loss, weights=[1.0 / self.num_outputs] * self.num_outputs)
+        if consistency is None:
+            from losses.pyramid_consistency import PyramidConsistencyLoss
+            consistency = PyramidConsistencyLoss()
+        self.consistency = consistency or None
+        self.labeled_bs = int(labeled_bs)
+        self.consistency_weight = consistency_weight
+        self.optimizer = FlatOptimizer(model, optimizer_name, **dict(optimizer_kwargs or {}))
+        if lr_scheduler_name == "poly":
+            self.lr_scheduler = PolyLRScheduler(self.optimizer, initial_lr=start_lr, max_steps=num_iters,
+                                                warmup_steps=lr_warmup_iter, interval=lr_interval)
+        elif lr_scheduler_name == "none":
+            self.lr_scheduler = None
+        else:
+            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
+        self.grad_norm = grad_norm
+        self.dyn = torch.zeros(2, device=self.optimizer.flat_param.device, dtype=torch.float32)  # {weight, unused}: MeanTeacherEngine's layout
+        self.current_iter = 0
+        self._one = None
+        self.last_supervised = self.last_consistency = None
+
+    def _write_dyn(self) -> None:
+        self.dyn[0].fill_(_ramp_value(self.consistency_weight, self.current_iter))  # the value travels as a launch argument: no host sync
+
+    def train_step(self, sampled_batch) -> torch.Tensor:
+        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
+        self.model.train()
+        if self.lr_scheduler:
+            self.lr_scheduler.step(self.current_iter)
+        dev = self.optimizer.flat_param.device
+        lb = self.labeled_bs
+        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
+        label = sampled_batch["label"].to(dev, non_blocking=True)
+        if image.ndim != 4:
+            raise NotImplementedError("URPCEngine implements 2-D inputs [B, C, H, W]")
+        if label.shape[0] < lb or image.shape[0] < lb:
+            raise ValueError(f"URPCEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
+        outs = self.model(image, return_ds=True, upsample_ds=False)
+        sup = self.supervised_loss([o[:lb] for o in outs], label[:lb])
+        self.last_supervised = sup.detach()
+        if self.consistency is not None and image.shape[0] > lb:
+            self._write_dyn()
+            loss = sup + self.consistency([o[lb:] for o in outs], dyn=self.dyn)
+            self.last_consistency = getattr(self.consistency, "last_value", None)
+        else:
+            loss = sup
+        self.optimizer.zero_grad()
+        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+            self._one = torch.ones_like(loss)
+        loss.backward(self._one)
+        self.optimizer.step(max_grad_norm=self.grad_norm)
+        self.current_iter += 1
+        return loss.detach()
+
+    def loss_value(self, loss: torch.Tensor) -> float:
+        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
+        v = float(loss.item())
+        ops.check_labels()
+        return v
+
+    @torch.no_grad()
+    def predict(self, image: torch.Tensor) -> torch.Tensor:
+        """eval forward (main output only) -> softmax -> argmax."""
+        self.model.eval()
+        out = self.model(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
+        return out.softmax(1).argmax(1)
+
+    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
+        """As `TrainEngine.save_state_dict` (model.pth, training_state.pth on request: the reference's layout); there is no second
+        network, hence no file beside them."""
+        from training import checkpoint
+        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+
+    def load_state_dict(self, save_path) -> dict:
+        from training import checkpoint
+        return checkpoint.load_state_dict(self, save_path)
