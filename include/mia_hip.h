@@ -633,6 +633,34 @@ int mia_urpc_fwd(const float* const* z, const int* factors, const int64_t* strid
                  const float* dyn_dev, int slabs, float* workspace, float* sums, float* terms, float* out, void* stream);
 int mia_urpc_bwd(const float* const* z, const int* factors, const int64_t* strides, float* const* dz, const int64_t* gstrides, int ns,
                  int nb, int H, int W, int k1, const float* sums, const float* dyn_dev, const float* grad_out, void* stream);
+/* Cross pseudo supervision (csrc/cps.hip; CPS: Chen et al., CVPR 2021; the reference has no such code): two networks' logits za and
+ * zb, both fp32, each addressed by its own (asn, ask, asp) / (bsn, bsk, bsp) element strides like mia_consistency_fwd (the layouts
+ * may differ; a batch slice of a larger tensor works), 1 <= k1 <= 8, N = nb * hw.  Per pixel:
+ *   ya = argmax_k za_k, yb = argmax_k zb_k on the fp32 logits themselves, a tie goes to the lowest index (numpy.argmax)
+ *   ca = (max_k softmax(za)_k >= tau), cb = (max_k softmax(zb)_k >= tau)   -- the confidence of the label's source
+ *   LA = (1/N) sum cb * (logsumexp(za) - za[yb]),  LB = (1/N) sum ca * (logsumexp(zb) - zb[ya])
+ * The denominator is always N: tau = 0 is F.cross_entropy(za, yb) + F.cross_entropy(zb, ya), and an empty mask gives 0, not NaN;
+ * the term is formed without the probability of the label, so a label whose soft-max is 0 in fp32 still has a finite term.
+ * dyn_dev: DEVICE array {weight, tau} of two fp32 values read by the kernels at run time (a captured step follows later writes), or
+ * NULL for weight 1, tau 0.  out[0] = weight * (LA + LB), out[1] = LA, out[2] = LB, out[3] = weight; counts = {sum ca, sum cb,
+ * sum (ya == yb)} as exact integers; code: byte map [nb][hw] = ya | yb << 3 | ca << 6 | cb << 7 that the backward reads instead of
+ * recomputing arg-max and threshold, so both directions agree on every pixel.  The backward writes, in ONE launch,
+ *   dza_j = grad_out * weight / N * cb * (softmax(za)_j - [j == yb])   to (gasn, gask, gasp) strides
+ *   dzb_j = grad_out * weight / N * ca * (softmax(zb)_j - [j == ya])   to (gbsn, gbsk, gbsp) strides
+ * (grad_out: device pointer to one float or NULL for 1); a pixel whose flag is clear gets exactly 0; labels and flags carry no
+ * gradient.  Block partials, then one finalize block in double / int64, in a fixed order, no atomics: bit-identical from run to run,
+ * and an image's code does not depend on the rest of the batch.  Four pixels per thread with 16-byte accesses for planar (sp == 1)
+ * and channels-last (sk == 1, sp == k1) tensors when hw % 4 == 0 and pointers / strides are 16-byte aligned (the rule of
+ * mia_consistency_fwd; each gradient must then have the layout class of its logits), one pixel per thread otherwise.  slabs =
+ * blocks per image of the forward; workspace: mia_cps_workspace 4-byte words.  Limits: nb * hw < 2^31.  Every check happens before
+ * any launch; nothing synchronises with the host. */
+int mia_cps_workspace(int nb, int slabs); /* 4-byte words; < 0 for a bad shape */
+int mia_cps_fwd(const float* za, const float* zb, const float* dyn_dev, int nb, int64_t hw, int k1, int64_t asn, int64_t ask,
+                int64_t asp, int64_t bsn, int64_t bsk, int64_t bsp, int slabs, float* workspace, unsigned char* code, float* out,
+                long long* counts, void* stream);
+int mia_cps_bwd(const float* za, const float* zb, const unsigned char* code, const float* dyn_dev, const float* grad_out, float* dza,
+                float* dzb, int nb, int64_t hw, int k1, int64_t asn, int64_t ask, int64_t asp, int64_t bsn, int64_t bsk, int64_t bsp,
+                int64_t gasn, int64_t gask, int64_t gasp, int64_t gbsn, int64_t gbsk, int64_t gbsp, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per

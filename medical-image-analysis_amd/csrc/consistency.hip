@@ -21,80 +21,7 @@
 // the batch; nothing synchronises with the host.
 //   ema_kernel            teacher = alpha teacher + (1 - alpha) student over flat fp32 buffers, in double, rounded once; 16-byte
 //                         accesses over the co-aligned body, scalar head and tail; alpha == 0 copies the student's bits
-#include "loss_common.h"
-
-enum { CS_SCALAR = 0, CS_PLANAR4 = 1, CS_CLAST4 = 2 };
-#define CS_PX(MODE) ((MODE) == CS_SCALAR ? 1 : 4)
-
-// Soft-max of one pixel in double: e_k = exp(z_k - max) in fp32, times (1 + the rounding error of the subtraction), so the only
-// fp32 error left in s_k is expf's own (bl_softmax of boundary.hip with the class count as a template parameter).
-template <int K1>
-__device__ __forceinline__ void cs_softmax(const float (&v)[K1], double (&s)[K1]) {
-  float mx = v[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) mx = fmaxf(mx, v[k]);
-  double se = 0.0;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) {
-    const float d = v[k] - mx;
-    const float t = d - v[k];
-    const float err = (v[k] - (d - t)) + (-mx - t);  // v - mx = d + err exactly
-    const float e = expf(d);
-    s[k] = (double)e + (double)e * (double)err;
-    se += s[k];
-  }
-  const double inv = 1.0 / se;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) s[k] *= inv;
-}
-
-// the logits of PX consecutive pixels from pixel p of one image (`img` = the image's first element)
-template <int K1, int MODE>
-__device__ __forceinline__ void cs_load(const float* __restrict__ img, int64_t p, const LossGeom& g, float (&v)[CS_PX(MODE)][K1]) {
-  if (MODE == CS_PLANAR4) {
-#pragma unroll
-    for (int k = 0; k < K1; ++k) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(img + k * g.sk + p);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i][k] = t[i];
-    }
-  } else if (MODE == CS_CLAST4) {  // four pixels = K1 consecutive 16-byte units
-    f32x4 f[K1];
-#pragma unroll
-    for (int u = 0; u < K1; ++u) f[u] = *reinterpret_cast<const f32x4*>(img + p * K1 + 4 * u);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) quad_unpack<K1>(f, i, v[i]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < K1; ++k) v[0][k] = img[p * g.sp + k * g.sk];
-  }
-}
-
-template <int K1, int MODE>
-__device__ __forceinline__ void cs_store(float* __restrict__ img, int64_t p, const LossGeom& g, const float (&v)[CS_PX(MODE)][K1]) {
-  if (MODE == CS_PLANAR4) {
-#pragma unroll
-    for (int k = 0; k < K1; ++k) {
-      f32x4 t;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) t[i] = v[i][k];
-      *reinterpret_cast<f32x4*>(img + k * g.sk + p) = t;
-      store_data_pad();  // the next unit's values may recycle t's registers (common.h)
-    }
-  } else if (MODE == CS_CLAST4) {
-#pragma unroll
-    for (int u = 0; u < K1; ++u) {
-      f32x4 t;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) t[i] = v[(4 * u + i) / K1][(4 * u + i) % K1];
-      *reinterpret_cast<f32x4*>(img + p * K1 + 4 * u) = t;
-      store_data_pad();
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < K1; ++k) img[p * g.sp + k * g.sk] = v[0][k];
-  }
-}
+#include "pixel_stream.h"  // the layout classes, cs_load / cs_store, cs_softmax and the dispatch, shared with cps.hip
 
 // u < threshold with u = -sum_k pbar_k log(pbar_k + 1e-6) in fp32 (a NaN in pbar or in the threshold keeps nothing)
 template <int K1>
@@ -238,15 +165,6 @@ __global__ __launch_bounds__(256) void cons_bwd_kernel(const float* __restrict__
   cs_store<K1, SM>(dl + b * go.sn, p, go, g);
 }
 
-static inline bool cs_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-// the four-pixel layout class of a logits-shaped tensor whose base and image stride are 16-byte aligned, else CS_SCALAR
-static int cs_mode(const void* base, const LossGeom& g, int k1) {
-  if (!cs_al16(base) || g.sn % 4 != 0) return CS_SCALAR;
-  if (g.sp == 1 && g.sk % 4 == 0) return CS_PLANAR4;
-  if (g.sk == 1 && g.sp == k1) return CS_CLAST4;
-  return CS_SCALAR;
-}
-
 template <int K1, int SM, int TM>
 static void cs_launch_fwd(hipStream_t st, const float* zs, const float* zt, const float* pbar, const float* dyn, int nb, int64_t hw,
                           const LossGeom& gs, const LossGeom& gt, int slabs, float* ws, int* wsn, unsigned char* keep) {
@@ -264,27 +182,6 @@ static void cs_launch_bwd(hipStream_t st, const float* zs, const float* zt, cons
   hipLaunchKernelGGL((cons_bwd_kernel<K1, SM, TM>), dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, st, zs, zt, keep, coef, dyn,
                      gout, dl, hw, total, gs, gt, go);
 }
-
-// FN<K1, SM, TM>(args...) for the run-time (k1, student mode, teacher mode); the modes are both CS_SCALAR or both four-pixel classes
-#define CS_MODES(FN, K, ...)                                                                        \
-  do {                                                                                              \
-    if (sm == CS_SCALAR) FN<K, CS_SCALAR, CS_SCALAR>(__VA_ARGS__);                                  \
-    else if (sm == CS_PLANAR4 && tm == CS_PLANAR4) FN<K, CS_PLANAR4, CS_PLANAR4>(__VA_ARGS__);      \
-    else if (sm == CS_PLANAR4) FN<K, CS_PLANAR4, CS_CLAST4>(__VA_ARGS__);                           \
-    else if (tm == CS_PLANAR4) FN<K, CS_CLAST4, CS_PLANAR4>(__VA_ARGS__);                           \
-    else FN<K, CS_CLAST4, CS_CLAST4>(__VA_ARGS__);                                                  \
-  } while (0)
-#define CS_DISPATCH(FN, ...)                            \
-  switch (k1) {                                         \
-    case 1: CS_MODES(FN, 1, __VA_ARGS__); break;        \
-    case 2: CS_MODES(FN, 2, __VA_ARGS__); break;        \
-    case 3: CS_MODES(FN, 3, __VA_ARGS__); break;        \
-    case 4: CS_MODES(FN, 4, __VA_ARGS__); break;        \
-    case 5: CS_MODES(FN, 5, __VA_ARGS__); break;        \
-    case 6: CS_MODES(FN, 6, __VA_ARGS__); break;        \
-    case 7: CS_MODES(FN, 7, __VA_ARGS__); break;        \
-    default: CS_MODES(FN, 8, __VA_ARGS__); break;       \
-  }
 
 extern "C" int mia_consistency_workspace(int nb, int slabs) {
   if (nb <= 0 || slabs <= 0 || (int64_t)nb * slabs * 3 > 0x7fffffff) return -1;

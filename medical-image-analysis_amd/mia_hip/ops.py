@@ -1698,6 +1698,70 @@ class PyramidConsistencyFn(torch.autograd.Function):
 PyramidConsistencyFn.last_out = PyramidConsistencyFn.last_terms = None
 
 
+# ------------------------------------------------------------------ cross pseudo supervision (two networks, hard pseudo-labels)
+CPS_MAX_CLASSES = 8
+
+
+class CrossPseudoFn(torch.autograd.Function):
+    """`apply(za, zb, dyn)` -> weight * (LA + LB), cross pseudo supervision between the logits [B, K, H, W] of two networks
+    (include/mia_hip.h: mia_cps_fwd; csrc/cps.hip): each is trained with cross-entropy on the arg-max of the other, where the other's
+    largest soft-max value reaches the threshold.  One streaming forward pass, and one streaming backward pass that writes BOTH
+    gradients.  fp32, any layout whose H and W collapse (planar, the head's channels-last view, a batch slice of either; the two may
+    differ).  `dyn` is None (weight 1, threshold 0: every pixel) or a DEVICE fp32 tensor {weight, threshold} that the kernels read
+    when they run.  By-products of the latest forward, all on the device: `last_out` = {weight * (LA + LB), LA, LB, weight},
+    `last_counts` (int64 [3]: confident pixels of A, of B, pixels where the two labels agree) and `last_code` (uint8 [B, H, W],
+    see `cps_decode`), which is also what the backward reads."""
+
+    @staticmethod
+    def forward(ctx, za, zb, dyn):
+        _need_dev(za, zb, dyn)
+        if za.ndim != 4:
+            raise NotImplementedError("the HIP cross pseudo supervision loss implements 2-D inputs [B, K, H, W]")
+        if zb.shape != za.shape:
+            raise MiaError(f"cross pseudo supervision: logits {tuple(za.shape)} and {tuple(zb.shape)} differ")
+        za, sa = _loss_logits(za)
+        zb, sb = _loss_logits(zb)
+        b, k1, h, w = za.shape
+        if dyn is not None:
+            if dyn.dtype != torch.float32 or dyn.numel() != 2 or not dyn.is_contiguous():
+                raise MiaError("cross pseudo supervision: `dyn` is two contiguous fp32 values {weight, threshold} on the device")
+            dyn = dyn.detach()
+        hw = h * w
+        dev = za.device
+        slabs = _consistency_slabs(hw)
+        words = max(lib().mia_cps_workspace(b, slabs), 0)  # < 0: a bad shape, reported by the call below
+        buf = torch.empty(words + 4, device=dev, dtype=torch.float32)  # workspace | out[4]: one allocation, every word written
+        ws, out = buf[:words], buf[words:]
+        counts = torch.empty(3, device=dev, dtype=torch.int64)
+        code = torch.empty((b, h, w), device=dev, dtype=torch.uint8)  # every byte is written by the forward kernel
+        call("mia_cps_fwd", _p(za), _p(zb), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(sa), *_strides_i64(sb), slabs, _p(ws), _p(code),
+             _p(out), _p(counts), _stream())
+        ctx.save_for_backward(za, zb)
+        ctx.code, ctx.dyn, ctx.sa, ctx.sb = code, dyn, sa, sb
+        CrossPseudoFn.last_out, CrossPseudoFn.last_counts, CrossPseudoFn.last_code = out, counts, code
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        za, zb = ctx.saved_tensors
+        b, k1, h, w = za.shape
+        dza, gsa, g = _loss_bwd_begin(za, gout)
+        dzb = torch.empty_like(zb)
+        call("mia_cps_bwd", _p(za), _p(zb), _p(ctx.code), _p(ctx.dyn), _p(g), _p(dza), _p(dzb), b, _c_i64(h * w), k1,
+             *_strides_i64(ctx.sa), *_strides_i64(ctx.sb), *_strides_i64(gsa), *_strides_i64(_pix_strides(dzb)), _stream())
+        return dza, dzb, None
+
+
+CrossPseudoFn.last_out = CrossPseudoFn.last_counts = CrossPseudoFn.last_code = None
+
+
+def cps_decode(code: torch.Tensor):
+    """(ya, yb, ca, cb) of `CrossPseudoFn.last_code`: the two label maps (int64) and the two confidence maps (bool), in plain tensor
+    ops on whatever device `code` lives on -- for logging and tests, not the hot path."""
+    c = code.to(torch.int64)
+    return c & 7, (c >> 3) & 7, ((c >> 6) & 1).bool(), ((c >> 7) & 1).bool()
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 

@@ -20,6 +20,11 @@ Out of scope:
 passes.  The network's own multi-scale outputs (`UNet(deep_supervision=True, ds_layer=n)`) are all supervised on the labelled images
 and asked to agree on the unlabelled ones (`losses.pyramid_consistency.PyramidConsistencyLoss`, csrc/urpc.hip).  Same batch
 convention, same device-resident schedule buffer `dyn`; it runs eagerly on one rank on 2-D inputs, with index labels.
+
+`CPSEngine` is cross pseudo supervision (CPS: Chen et al., CVPR 2021), the two-network row of those tables: two networks of different
+initialisation, both trained, each on the supervised loss plus cross-entropy on the other's hard pseudo-labels
+(`losses.cross_pseudo.CrossPseudoSupervisionLoss`, csrc/cps.hip).  One `backward()` feeds two `FlatOptimizer`s.  Same batch
+convention and `dyn = {weight, confidence threshold}`; eager, one rank, 2-D inputs.  Out of scope: CutMix-CPS, Dice on pseudo-labels.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ from scheduler.lr_scheduler import PolyLRScheduler
 from training.engine import FlatOptimizer
 
 TEACHER_FILE = "mean_teacher.pth"
+CPS_PEER_FILE = "cps_peer.pth"
 
 
 def ema_alpha(step: int, ema_decay: float) -> float:
@@ -356,3 +362,156 @@ class URPCEngine:
     def load_state_dict(self, save_path) -> dict:
         from training import checkpoint
         return checkpoint.load_state_dict(self, save_path)
+
+
+class CPSEngine:
+    """two networks + supervised loss on the labelled images for each + cross pseudo supervision between them + two flat optimizers +
+    two poly LR schedules.  `train_step` returns the loss TENSOR (no host sync); `last_supervised`, `last_cps` (the unweighted
+    LA + LB), `last_agree` (int64: pixels of the CPS slice where the two arg-max labels agree) and `last_confident` (int64 [2]) are
+    device by-products of the latest step.  Per step
+
+        out_a = model_a(image);  out_b = model_b(image)
+        sup   = supervised_loss(out_a[:lb], label[:lb]) + supervised_loss(out_b[:lb], label[:lb])
+        s     = 0 if cps_on_labeled else lb        # the paper uses every image, SSL4MIS the unlabelled ones only
+        loss  = sup + cps(out_a[s:], out_b[s:], dyn=dyn)      # skipped when that slice is empty
+        one backward; clip and step each optimizer on its own
+
+    model_a, model_b: two `UNet`s with the same class count and different initialisations (two objects: the same object twice is an
+    error).  `self.model` / `self.optimizer` / `self.lr_scheduler` are network A's, so `training/checkpoint.py` serves it unchanged;
+    network B's carry the suffix `_b`.
+    cps_weight, confidence_threshold: a float or an object with `.step(i)`; each step the engine writes `weight_i` and `tau_i` into the
+    device buffer `dyn` before anything reads it, outside the autograd graph.  tau = 0 (the default) is the published CPS; tau > 0
+    lets a network learn only from labels whose source gives them a soft-max of at least tau."""
+
+    def __init__(self, model_a, model_b, supervised_loss, labeled_bs: int, cps_weight=0.1, confidence_threshold=0.0,
+                 cps_on_labeled: bool = False, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
+                 start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
+                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
+            raise NotImplementedError("CPSEngine runs on one rank")
+        if labeled_bs < 1:
+            raise ValueError("CPSEngine: labeled_bs must be at least 1")
+        if model_a is model_b:
+            raise ValueError("CPSEngine needs two networks: model_a and model_b are the same object")
+        ka, kb = (int(m.decoder.seg_output.weight.shape[0]) for m in (model_a, model_b))
+        if ka != kb:
+            raise ValueError(f"CPSEngine: the networks predict {ka} and {kb} classes")
+        if lr_scheduler_name not in ("poly", "none"):
+            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
+        self.model, self.model_b = model_a, model_b
+        self.supervised_loss = supervised_loss
+        self.labeled_bs = int(labeled_bs)
+        self.cps_weight, self.confidence_threshold = cps_weight, confidence_threshold
+        self.cps_on_labeled = bool(cps_on_labeled)
+        self.num_classes = ka  # K: background included
+        self.optimizer = FlatOptimizer(model_a, optimizer_name, **dict(optimizer_kwargs or {}))
+        self.optimizer_b = FlatOptimizer(model_b, optimizer_name, **dict(optimizer_kwargs or {}))
+        if self.optimizer.flat_param.device != self.optimizer_b.flat_param.device:
+            raise ValueError("CPSEngine: the two networks live on different devices")
+        self.lr_scheduler = self.lr_scheduler_b = None
+        if lr_scheduler_name == "poly":
+            self.lr_scheduler, self.lr_scheduler_b = (PolyLRScheduler(o, initial_lr=start_lr, max_steps=num_iters,
+                                                                      warmup_steps=lr_warmup_iter, interval=lr_interval)
+                                                      for o in (self.optimizer, self.optimizer_b))
+        self.grad_norm = grad_norm
+        from losses.cross_pseudo import CrossPseudoSupervisionLoss
+        self.cps = CrossPseudoSupervisionLoss(self.num_classes - 1)
+        self.dyn = torch.zeros(2, device=self.optimizer.flat_param.device, dtype=torch.float32)  # {weight, tau}, read by the kernels
+        self.current_iter = 0
+        self._one = None
+        self.last_supervised = self.last_cps = self.last_agree = self.last_confident = None
+
+    def _write_dyn(self) -> None:
+        self.dyn[0].fill_(_ramp_value(self.cps_weight, self.current_iter))  # the values travel as launch arguments: no host sync
+        self.dyn[1].fill_(_ramp_value(self.confidence_threshold, self.current_iter))
+
+    def train_step(self, sampled_batch) -> torch.Tensor:
+        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
+        self.model.train()
+        self.model_b.train()
+        for sched in (self.lr_scheduler, self.lr_scheduler_b):
+            if sched:
+                sched.step(self.current_iter)
+        dev = self.optimizer.flat_param.device
+        lb = self.labeled_bs
+        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
+        label = sampled_batch["label"].to(dev, non_blocking=True)
+        if image.ndim != 4:
+            raise NotImplementedError("CPSEngine implements 2-D inputs [B, C, H, W]")
+        if label.shape[0] < lb or image.shape[0] < lb:
+            raise ValueError(f"CPSEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
+        out_a = self.model(image)
+        out_b = self.model_b(image)
+        sup = self.supervised_loss(out_a[:lb], label[:lb]) + self.supervised_loss(out_b[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        s = 0 if self.cps_on_labeled else lb
+        if image.shape[0] > s:
+            self._write_dyn()
+            loss = sup + self.cps(out_a[s:], out_b[s:], dyn=self.dyn)
+            self.last_cps = self.cps.last_value_a + self.cps.last_value_b
+            self.last_agree, self.last_confident = self.cps.last_agree, self.cps.last_confident
+        else:
+            loss = sup
+        self.optimizer.zero_grad()
+        self.optimizer_b.zero_grad()
+        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+            self._one = torch.ones_like(loss)
+        loss.backward(self._one)
+        self.optimizer.step(max_grad_norm=self.grad_norm)
+        self.optimizer_b.step(max_grad_norm=self.grad_norm)
+        # B's step moved the parameter epoch on after A's packed weights were rebuilt; A's parameters have not changed since
+        plan = self.optimizer._pack_plan
+        if plan is not None and plan.valid():
+            plan.plant()
+        self.current_iter += 1
+        return loss.detach()
+
+    def loss_value(self, loss: torch.Tensor) -> float:
+        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
+        v = float(loss.item())
+        ops.check_labels()
+        return v
+
+    @torch.no_grad()
+    def predict(self, image: torch.Tensor, use: str = "a") -> torch.Tensor:
+        """eval forward -> arg-max of the soft-max of network "a", of network "b", or of the "mean" of the two soft-maxes
+        (`inference.predictor.softmax_accum`: ties to the lowest class)."""
+        if use not in ("a", "b", "mean"):
+            raise ValueError(f'CPSEngine.predict: use="{use}" is none of "a", "b", "mean"')
+        image = image.to(self.optimizer.flat_param.device, dtype=torch.float32)
+        if use != "mean":
+            net = self.model if use == "a" else self.model_b
+            net.eval()
+            return net(image).softmax(1).argmax(1)
+        from inference.predictor import softmax_accum
+        self.model.eval()
+        self.model_b.eval()
+        za = self.model(image)
+        prob = torch.empty(za.shape, device=za.device, dtype=torch.float32)
+        pred = torch.empty((za.shape[0],) + tuple(za.shape[2:]), device=za.device, dtype=torch.int64)
+        softmax_accum(za, prob, None, weight=0.5, first=True)
+        softmax_accum(self.model_b(image), prob, pred, weight=0.5)
+        return pred
+
+    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
+        """Network A as `TrainEngine.save_state_dict` writes it (model.pth, training_state.pth on request: the reference's layout);
+        network B's `state_dict` -- and on request its optimizer state, in the same torch.optim format -- in a file of its own."""
+        from training import checkpoint
+        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+        peer = {"model": checkpoint.model_state_for_save(self.model_b)}
+        if save_training_state:
+            peer["optimizer"] = checkpoint.optimizer_state_to_torch(self.optimizer_b, self.model_b)
+            peer["optimizer"]["step_count"] = int(self.optimizer_b.step_count)
+        torch.save(peer, Path(save_path) / CPS_PEER_FILE)
+
+    def load_state_dict(self, save_path) -> dict:
+        from training import checkpoint
+        out = checkpoint.load_state_dict(self, save_path)
+        pf = Path(save_path) / CPS_PEER_FILE
+        if pf.is_file():
+            sd = torch.load(pf, map_location=self.optimizer_b.flat_param.device, weights_only=True)
+            self.model_b.load_state_dict(sd["model"])  # copy_ into the flat-buffer views
+            if "optimizer" in sd:
+                checkpoint.optimizer_state_from_torch(self.optimizer_b, self.model_b, sd["optimizer"])
+        ops.bump_param_epoch()  # packed weights of both networks are stale now
+        return out
