@@ -218,6 +218,10 @@ __global__ void rot_flip_kernel(const T* __restrict__ in, T* __restrict__ out, i
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t bc = i / ohw, p = i - bc * ohw;
     int y = (int)(p / ow), x = (int)(p - (int64_t)y * ow);
+    // the flips act on the ROTATED image (out = flip(rot90(in, k))): undo them on the output coordinates first.  (Flipping the
+    // source coordinates instead is the same for even k and for both flips at once, but swaps the two flips for odd k.)
+    if (flip_h) y = oh - 1 - y;
+    if (flip_w) x = ow - 1 - x;
     int sy, sx;
     // torch.rot90(x, k, (H, W)): k=1 -> out[y][x] = in[x][W-1-y]
     switch (k & 3) {
@@ -226,8 +230,6 @@ __global__ void rot_flip_kernel(const T* __restrict__ in, T* __restrict__ out, i
       case 2: sy = h - 1 - y; sx = w - 1 - x; break;
       default: sy = h - 1 - x; sx = y; break;
     }
-    if (flip_h) sy = h - 1 - sy;
-    if (flip_w) sx = w - 1 - sx;
     out[i] = in[bc * (int64_t)h * w + (int64_t)sy * w + sx];
   }
 }
@@ -329,8 +331,17 @@ extern "C" int mia_gaussian_blur(const float* in, float* out, int nb, int c, int
   return MIA_OK;
 }
 
-// ---------------------------------------------------------------- per-sample statistics over C*H*W: stats[b] = (sum, sumsq) in double
+// ---------------------------------------------------------------- per-sample statistics over C*H*W: out[b] = (mean, unbiased std)
 // gray=1 with c==3: statistics of 0.2989 r + 0.587 g + 0.114 b (torchvision rgb_to_grayscale) over H*W.
+// The fp32 partial sums are taken about a per-sample pivot K (the sample's first value): s1 = sum(v - K), s2 = sum((v - K)^2),
+// mean = K + s1 / n, var = (s2 - s1^2 / n) / (n - 1).  Sums of the raw v and v^2 lose the variance of a low-contrast image to
+// cancellation (mean 0.9 / std 0.002: std off by 1e-3); about a pivot inside the data the summands are of the size of the spread.
+// Both kernels compute K with this one function (contraction off), so they use the same bits.
+__device__ __forceinline__ float stats_pivot(const float* __restrict__ src, int64_t hw, bool luma) {
+#pragma clang fp contract(off)
+  return luma ? (0.2989f * src[0] + 0.587f * src[hw]) + 0.114f * src[2 * hw] : src[0];
+}
+
 __global__ void sample_stats_partial_kernel(const float* __restrict__ in, int c, int64_t hw, int gray, int slabs,
                                             float* __restrict__ part, const int* __restrict__ apply) {
   __shared__ float red[16];
@@ -342,23 +353,35 @@ __global__ void sample_stats_partial_kernel(const float* __restrict__ in, int c,
   const int64_t n = (gray && c == 3) ? hw : (int64_t)c * hw;
   const int64_t per = (n + slabs - 1) / slabs, r0 = s * per, r1 = r0 + per < n ? r0 + per : n;
   const float* src = in + (int64_t)b * c * hw;
+  const float pivot = stats_pivot(src, hw, gray && c == 3);
   float s1 = 0.f, s2 = 0.f;
   for (int64_t i = r0 + threadIdx.x; i < r1; i += blockDim.x) {
-    const float v = (gray && c == 3) ? (0.2989f * src[i] + 0.587f * src[hw + i] + 0.114f * src[2 * hw + i]) : src[i];
+    const float v = ((gray && c == 3) ? (0.2989f * src[i] + 0.587f * src[hw + i] + 0.114f * src[2 * hw + i]) : src[i]) - pivot;
     s1 += v; s2 += v * v;
   }
   float r = block_sum(s1, red); if (threadIdx.x == 0) part[(size_t)blockIdx.x * 2] = r;
   r = block_sum(s2, red); if (threadIdx.x == 0) part[(size_t)blockIdx.x * 2 + 1] = r;
 }
 
-__global__ void sample_stats_final_kernel(const float* __restrict__ part, int nb, int slabs, int64_t n, float* __restrict__ out) {
-  // out[b] = (mean, unbiased std)
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= nb) return;
+// one wave per sample: lane s takes slab s, the fp64 totals come from a butterfly over the wave (a fixed order: the same bits whichever
+// variant launched it); the pivot is read again from the sample itself
+__global__ void sample_stats_final_kernel(const float* __restrict__ part, const float* __restrict__ in, int c, int64_t hw, int gray,
+                                          int slabs, float* __restrict__ out, const int* __restrict__ apply) {
+  // out[b] = (mean, unbiased std); a skipped sample is not read, its row is zero
+  const int b = blockIdx.x, l = threadIdx.x;  // blockDim.x == 64
+  if (skipped(apply, b)) {  // uniform per block
+    if (l == 0) { out[b * 2] = 0.f; out[b * 2 + 1] = 0.f; }
+    return;
+  }
+  const int64_t n = (gray && c == 3) ? hw : (int64_t)c * hw;
+  const double pivot = (double)stats_pivot(in + (int64_t)b * c * hw, hw, gray && c == 3);
   double s1 = 0, s2 = 0;
-  for (int s = 0; s < slabs; ++s) { s1 += part[((size_t)b * slabs + s) * 2]; s2 += part[((size_t)b * slabs + s) * 2 + 1]; }
-  const double mean = s1 / (double)n;
-  double var = n > 1 ? (s2 - (double)n * mean * mean) / (double)(n - 1) : 0.0;
+  for (int s = l; s < slabs; s += 64) { s1 += part[((size_t)b * slabs + s) * 2]; s2 += part[((size_t)b * slabs + s) * 2 + 1]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+  if (l != 0) return;
+  const double mean = pivot + s1 / (double)n;
+  double var = n > 1 ? (s2 - s1 * s1 / (double)n) / (double)(n - 1) : 0.0;
   if (var < 0) var = 0;
   out[b * 2] = (float)mean;
   out[b * 2 + 1] = (float)sqrt(var);
@@ -404,8 +427,7 @@ static int sample_stats_run(const float* in, int nb, int c, int64_t hw, int gray
   MIA_CHECK_ARG(in && workspace && mean_std && nb > 0 && c > 0 && hw > 0, "mia_sample_stats: bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(sample_stats_partial_kernel, dim3(nb * STAT_SLABS), dim3(256), 0, st, in, c, hw, gray, STAT_SLABS, workspace, apply);
-  const int64_t n = (gray && c == 3) ? hw : (int64_t)c * hw;
-  hipLaunchKernelGGL(sample_stats_final_kernel, dim3(ceil_div(nb, 64)), dim3(64), 0, st, workspace, nb, STAT_SLABS, n, mean_std);
+  hipLaunchKernelGGL(sample_stats_final_kernel, dim3(nb), dim3(64), 0, st, workspace, in, c, hw, gray, STAT_SLABS, mean_std, apply);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }

@@ -2,7 +2,12 @@
 parameters, and against vectors produced by the reference's own transforms (tests/golden/transforms.npz)
 where the reference is runnable (gamma, noise, low-res, rot90, mirror, z-score).  The torchvision-backed
 transforms (affine, rotation, blur, contrast, resize) are PARITY UNPINNED: they are checked against the
-oracle's restatement of torchvision's algorithm plus analytic known answers."""
+oracle's restatement of torchvision's algorithm plus analytic known answers.
+
+Kernel-level coverage of the same kernels -- every dispatch edge against a float64 restatement (grid-stride second trips, apply flags,
+in-place ops, the bilinear adjoint, Philox known answers, low-contrast statistics) -- is in tests/test_gpu_augment.py (restatement:
+tests/_augment_ref.py, checked on the CPU by tests/test_augment_host.py); the argmax / Dice / selector-score reductions are in
+tests/test_gpu_metrics.py (tests/_metrics_ref.py, tests/test_metrics_host.py)."""
 import os
 
 import numpy as np
