@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void bl_fwd_kernel(const float* __restrict__ l
       if (k < k1) acc += sm[k] * (double)d[k];
   }
   if (bad) *bad_label = 1;
-  const float hi = (float)acc;
-  const float part[2] = {hi, (float)(acc - (double)hi)};
+  float part[2];
+  loss_split(acc, part);
   auto red = loss_block_sums<2, 0>();
   red.put(0, part);
   __syncthreads();
@@ -194,17 +194,11 @@ __global__ __launch_bounds__(256) void bl_fwd_kernel(const float* __restrict__ l
 // one block: out[0] = weight * L, out[1] = L, out[2] = weight; coef[0] = 1 (NaN after a bad label: every gradient follows)
 __global__ void bl_finalize_kernel(const float* __restrict__ ws, int nparts, double n_terms, const float* __restrict__ weight_dev,
                                    float* __restrict__ coef, float* __restrict__ out, int* __restrict__ bad_label) {
-  __shared__ double dsum[256];
-  double my = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) my += (double)ws[(size_t)i * 2] + (double)ws[(size_t)i * 2 + 1];
-  dsum[threadIdx.x] = my;
-  __syncthreads();
+  const LossTotals tot = loss_totals<1, 0>(ws, nullptr, nparts, 1);
   __shared__ float res[3];
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < (int)blockDim.x; ++i) t += dsum[i];
     const float wt = weight_dev ? weight_dev[0] : 1.f;
-    const double l = t / n_terms;
+    const double l = tot.f[0] / n_terms;
     res[0] = (float)((double)wt * l);
     res[1] = (float)l;
     res[2] = wt;

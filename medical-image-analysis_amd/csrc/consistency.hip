@@ -82,8 +82,8 @@ __global__ __launch_bounds__(256) void cons_fwd_kernel(const float* __restrict__
         kd[0] = (unsigned char)kp[0];
     }
   }
-  const float hi = (float)acc;
-  const float part[2] = {hi, (float)(acc - (double)hi)};
+  float part[2];
+  loss_split(acc, part);
   const int cpart[1] = {cnt};
   auto red = loss_block_sums<2, 1>();
   red.put(0, part, 0, cpart);
@@ -96,22 +96,11 @@ __global__ __launch_bounds__(256) void cons_fwd_kernel(const float* __restrict__
 __global__ void cons_finalize_kernel(const float* __restrict__ ws, const int* __restrict__ wsn, int nparts, int masked, double n_all,
                                      double den_scale, const float* __restrict__ dyn, float* __restrict__ coef,
                                      float* __restrict__ out, long long* __restrict__ n_keep) {
-  __shared__ double dsum[256];
-  __shared__ long long nsum[256];
-  double my = 0.0;
-  long long mn = 0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    my += (double)ws[(size_t)i * 2] + (double)ws[(size_t)i * 2 + 1];
-    mn += wsn[i];
-  }
-  dsum[threadIdx.x] = my;
-  nsum[threadIdx.x] = mn;
-  __syncthreads();
+  const LossTotals tot = loss_totals<1, 1>(ws, wsn, nparts, 1);
   __shared__ float res[3];
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    long long n = 0;
-    for (int i = 0; i < (int)blockDim.x; ++i) { t += dsum[i]; n += nsum[i]; }
+    const double t = tot.f[0];
+    const long long n = tot.n[0];
     const float wt = dyn ? dyn[0] : 1.f;
     const double den = masked ? den_scale * (double)n + 1e-16 : n_all;
     const double l = t / den;  // nothing kept: 0 / 1e-16 = 0

@@ -24,12 +24,6 @@
 
 #define CPS_WORDS 7  // per block: (hi, lo) of the two sums, three counts
 
-__device__ __forceinline__ double cps_wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // arg-max of the fp32 logits, the lowest index among equals; mx = the maximum.  Plain compares and selects over compile-time indices:
 // no register array is indexed at run time.
 template <int K1>
@@ -116,12 +110,10 @@ __global__ __launch_bounds__(256) void cps_fwd_kernel(const float* __restrict__ 
       cd[0] = (unsigned char)bits;
   }
   // the wave's sums in double first, so that the float pairs below are added four at a time only
-  acc_a = cps_wave_sum_d(acc_a);
-  acc_b = cps_wave_sum_d(acc_b);
-  if ((threadIdx.x & 63) != 0) acc_a = acc_b = 0.0;
-  const float ha = (float)acc_a, hb = (float)acc_b;
-  const float part[4] = {ha, (float)(acc_a - (double)ha), hb, (float)(acc_b - (double)hb)};
   auto red = loss_block_sums<4, 3>();
+  float part[4];
+  loss_wave_pair(acc_a, red.l, part);
+  loss_wave_pair(acc_b, red.l, part + 2);
   red.put(0, part, 0, cnt);
   __syncthreads();
   if (threadIdx.x < 4) ws[(size_t)blockIdx.x * 4 + threadIdx.x] = red.sum_f(threadIdx.x);
@@ -131,42 +123,19 @@ __global__ __launch_bounds__(256) void cps_fwd_kernel(const float* __restrict__ 
 // one block: out = {weight (LA + LB), LA, LB, weight}; counts = {sum ca, sum cb, sum [ya == yb]}
 __global__ void cps_finalize_kernel(const float* __restrict__ ws, const int* __restrict__ wsn, int nparts, double n_all,
                                     const float* __restrict__ dyn, float* __restrict__ out, long long* __restrict__ counts) {
-  __shared__ double dsum[2][256];
-  __shared__ long long nsum[3][256];
-  double my[2] = {0.0, 0.0};
-  long long mn[3] = {0, 0, 0};
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) {
-    my[0] += (double)ws[(size_t)i * 4] + (double)ws[(size_t)i * 4 + 1];
-    my[1] += (double)ws[(size_t)i * 4 + 2] + (double)ws[(size_t)i * 4 + 3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) mn[c] += wsn[(size_t)i * 3 + c];
-  }
-  dsum[0][threadIdx.x] = my[0];
-  dsum[1][threadIdx.x] = my[1];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) nsum[c][threadIdx.x] = mn[c];
-  __syncthreads();
+  const LossTotals tot = loss_totals<2, 3>(ws, wsn, nparts, 2);
   __shared__ float res[4];
-  __shared__ long long nres[3];
-  if (threadIdx.x < 2) {  // LA, LB
-    double t = 0.0;
-    for (int i = 0; i < (int)blockDim.x; ++i) t += dsum[threadIdx.x][i];
-    dsum[threadIdx.x][0] = t / n_all;
-    res[1 + threadIdx.x] = (float)(t / n_all);
-  } else if (threadIdx.x < 5) {
-    long long n = 0;
-    for (int i = 0; i < (int)blockDim.x; ++i) n += nsum[threadIdx.x - 2][i];
-    nres[threadIdx.x - 2] = n;
-  }
-  __syncthreads();
   if (threadIdx.x == 0) {
+    const double la = tot.f[0] / n_all, lb = tot.f[1] / n_all;
     const float wt = dyn ? dyn[0] : 1.f;
-    res[0] = (float)((double)wt * (dsum[0][0] + dsum[1][0]));
+    res[0] = (float)((double)wt * (la + lb));
+    res[1] = (float)la;
+    res[2] = (float)lb;
     res[3] = wt;
   }
   __syncthreads();
   if (threadIdx.x < 4) out[threadIdx.x] = res[threadIdx.x];  // one 4-byte store per lane
-  else if (threadIdx.x < 7) counts[threadIdx.x - 4] = nres[threadIdx.x - 4];
+  else if (threadIdx.x < 7) counts[threadIdx.x - 4] = tot.n[threadIdx.x - 4];
 }
 
 // Between the two gradients: the address arithmetic of the second one may recycle the data registers of the first one's last

@@ -1,5 +1,6 @@
-// What the loss kernels share (dice_ce.hip, seg_loss.hip, region_loss.hip, ds_loss.hip): ONE definition of each piece, so that the
-// files cannot drift apart.  Arithmetic that differs between the losses stays in their own files.
+// What the loss kernels share (dice_ce.hip, seg_loss.hip, region_loss.hip, ds_loss.hip, and the streaming losses boundary.hip,
+// consistency.hip, cps.hip, urpc.hip): ONE definition of each piece, so that the files cannot drift apart.  Arithmetic that differs
+// between the losses stays in their own files.
 #pragma once
 #include "common.h"
 
@@ -90,6 +91,65 @@ __device__ __forceinline__ LossBlockSums<NF, NI> loss_block_sums() {
   __shared__ float f[4][NF];
   __shared__ int i[4][NI ? NI : 1];
   return {f, i, (int)(threadIdx.x >> 6), (int)(threadIdx.x & 63)};
+}
+
+// ---- double-precision sums that travel as float pairs (boundary.hip, consistency.hip, cps.hip, urpc.hip)
+// A block's sum is kept in double, parked as hi = (float)v, lo = (float)(v - hi), and read back as (double)hi + (double)lo.
+__device__ __forceinline__ void loss_split(double v, float* p) {
+  p[0] = (float)v;
+  p[1] = (float)(v - (double)p[0]);
+}
+
+// The wave's sum of v in double as a pair in lane 0, zeros in the other lanes: LossBlockSums::put() then adds one pair and 63 zeros
+// in fp32, which is exact (a pair summed in fp32 across the wave would round at every level).  boundary.hip and consistency.hip park
+// a pair per THREAD instead and let put() add them in fp32; the two forms round differently and each kernel keeps its own.
+__device__ __forceinline__ void loss_wave_pair(double v, int lane, float* p) {
+  loss_split(wave_sum_d(v), p);
+  p[0] = lane == 0 ? p[0] : 0.f;
+  p[1] = lane == 0 ? p[1] : 0.f;
+}
+
+// The head of a finalize kernel (one block of 256 threads): the totals of nq <= MAXQ quantities whose per-block pairs lie in
+// part [nparts][nq][2], and of NC counts in cnt [nparts][NC].  A thread adds hi + lo of parts t, t + 256, ... in double (counts in
+// int64) into its entry of a 256-entry LDS array per quantity; then one thread per quantity adds the 256 entries in index order.  The
+// sequence of additions of every quantity is fixed, so the totals are bit-identical run to run.  f[q] and n[c] are LDS and valid in
+// every thread on return.
+struct LossTotals {
+  const double* f;
+  const long long* n;
+};
+template <int MAXQ, int NC>
+__device__ __forceinline__ LossTotals loss_totals(const float* __restrict__ part, const int* __restrict__ cnt, int nparts, int nq) {
+  static_assert(MAXQ <= 64, "one thread of the first wave per quantity");
+  __shared__ double fsh[MAXQ][256], ftot[MAXQ];
+  __shared__ long long nsh[NC ? NC : 1][256], ntot[NC ? NC : 1];
+  for (int q = 0; q < nq; ++q) {
+    double my = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+      const float* o = part + ((size_t)i * nq + q) * 2;
+      my += (double)o[0] + (double)o[1];
+    }
+    fsh[q][threadIdx.x] = my;
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    long long my = 0;
+    for (int i = threadIdx.x; i < nparts; i += 256) my += cnt[(size_t)i * NC + c];
+    nsh[c][threadIdx.x] = my;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < nq) {
+    double s = 0.0;
+    for (int i = 0; i < 256; ++i) s += fsh[t][i];
+    ftot[t] = s;
+  } else if (t >= 64 && t < 64 + NC) {  // the counts in the second wave, beside the sums
+    long long s = 0;
+    for (int i = 0; i < 256; ++i) s += nsh[t - 64][i];
+    ntot[t - 64] = s;
+  }
+  __syncthreads();
+  return {ftot, ntot};
 }
 
 // The tail of every finalize kernel (one block), after out[0..3) and coef[0..ncoef) are written.

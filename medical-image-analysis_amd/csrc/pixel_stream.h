@@ -1,7 +1,8 @@
 // What the two-tensor streaming losses share (consistency.hip, cps.hip): the layout classes of a logits-shaped tensor, the loads and
 // stores of one thread's pixel group in each class, the per-pixel soft-max in double, and the host-side dispatch over
 // (class count, layout class of the first tensor, layout class of the second).  ONE definition of each piece, so that the files
-// cannot drift apart (loss_common.h, ds_common.h).
+// cannot drift apart (loss_common.h, ds_common.h).  Their double-precision partial sums, which boundary.hip and urpc.hip use too, are in
+// loss_common.h.
 #pragma once
 #include "loss_common.h"
 

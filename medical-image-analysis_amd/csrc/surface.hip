@@ -148,11 +148,6 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Pass 3: block (n, slab of rows), 256 threads.  A row without a query voxel is skipped after reading its query bytes; otherwise its
 // three fields are staged in LDS and each query voxel scans its row.  Partials are written to five separate arrays (4-byte stores).

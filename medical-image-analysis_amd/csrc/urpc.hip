@@ -36,12 +36,6 @@ struct UrpcScales {
   int id[URPC_MAXS];  // the scale's row in sums
 };
 
-__device__ __forceinline__ double urpc_wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // p_s, lp_s of every scale and m at full-resolution pixel (Y, X) of image b
 template <int NK, int NS>
 __device__ __forceinline__ void urpc_pixel(const UrpcScales& a, int b, int Y, int X, int H, int W, int k1, float (&p)[NS][NK],
@@ -124,16 +118,13 @@ __global__ __launch_bounds__(256) void urpc_fwd_kernel(UrpcScales a, int H, int 
       acc[s][2] += (double)v[s];
     }
   }
-  // the wave sum runs in double (a (hi, lo) pair summed in fp32 would round at every level); lane 0 parks the pair, the other lanes
-  // add zeros, so the fp32 sums inside put() are exact
   auto red = loss_block_sums<6 * NS, 0>();
 #pragma unroll
   for (int s = 0; s < NS; ++s)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      const double t = urpc_wave_sum_d(acc[s][j]);
-      const float hi = (float)t;
-      const float pr[2] = {red.l == 0 ? hi : 0.f, red.l == 0 ? (float)(t - (double)hi) : 0.f};
+      float pr[2];
+      loss_wave_pair(acc[s][j], red.l, pr);
       red.put((s * 3 + j) * 2, pr);
     }
   __syncthreads();
@@ -142,10 +133,7 @@ __global__ __launch_bounds__(256) void urpc_fwd_kernel(UrpcScales a, int H, int 
     double tot = 0.0;
 #pragma unroll
     for (int wv = 0; wv < 4; ++wv) tot += (double)red.f[wv][2 * t] + (double)red.f[wv][2 * t + 1];
-    const float hi = (float)tot;
-    float* o = part + ((size_t)blockIdx.x * 3 * NS + t) * 2;
-    o[0] = hi;
-    o[1] = (float)(tot - (double)hi);
+    loss_split(tot, part + ((size_t)blockIdx.x * 3 * NS + t) * 2);
   }
 }
 
@@ -153,25 +141,8 @@ __global__ __launch_bounds__(256) void urpc_fwd_kernel(UrpcScales a, int H, int 
 __global__ __launch_bounds__(256) void urpc_finalize_kernel(const float* __restrict__ part, int nparts, int ns, int k1, double npix,
                                                             const float* __restrict__ dyn, float* __restrict__ sums,
                                                             float* __restrict__ terms, float* __restrict__ out) {
-  __shared__ double sh[3 * URPC_MAXS][256];
-  __shared__ double tot[3 * URPC_MAXS];
-  const int nq = 3 * ns;
-  for (int q = 0; q < nq; ++q) {
-    double my = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) {
-      const float* o = part + ((size_t)i * nq + q) * 2;
-      my += (double)o[0] + (double)o[1];
-    }
-    sh[q][threadIdx.x] = my;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nq) {
-    double t = 0.0;
-    for (int i = 0; i < 256; ++i) t += sh[threadIdx.x][i];
-    tot[threadIdx.x] = t;
-    sums[threadIdx.x] = (float)t;
-  }
-  __syncthreads();
+  const double* tot = loss_totals<3 * URPC_MAXS, 0>(part, nullptr, nparts, 3 * ns).f;
+  if ((int)threadIdx.x < 3 * ns) sums[threadIdx.x] = (float)tot[threadIdx.x];
   if (threadIdx.x == 0) {
     double l = 0.0;
     for (int s = 0; s < ns; ++s) {

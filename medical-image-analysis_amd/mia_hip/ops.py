@@ -1191,6 +1191,28 @@ def _loss_logits(logits: torch.Tensor):
     return logits, st
 
 
+def _loss_logits_pair(who: str, a: torch.Tensor, b: torch.Tensor, differ: str):
+    """The opening of the losses between two logits tensors: `a` and `b` ([B, K, H, W], one shape) each through `_loss_logits`, as
+    (a, a's strides, b, b's strides).  `differ` is the text of the shape error, with {a} and {b} for the two shapes."""
+    if a.ndim != 4:
+        raise NotImplementedError(f"the HIP {who} implements 2-D inputs [B, K, H, W]")
+    if b.shape != a.shape:
+        raise MiaError(differ.format(a=tuple(a.shape), b=tuple(b.shape)))
+    return _loss_logits(a) + _loss_logits(b)
+
+
+def _dyn_arg(who: str, dyn: Optional[torch.Tensor], numel: int, exact: bool) -> Optional[torch.Tensor]:
+    """The run-time schedule buffer of a loss: None, or a contiguous fp32 device tensor of `numel` values (at least `numel` unless
+    `exact`), detached."""
+    if dyn is None:
+        return None
+    if dyn.dtype != torch.float32 or not dyn.is_contiguous() or (dyn.numel() != numel if exact else dyn.numel() < numel):
+        what = "two contiguous fp32 values {weight, threshold} on the device" if exact else \
+            "a contiguous fp32 device tensor whose first element is the weight"
+        raise MiaError(f"{who}: `dyn` is {what}")
+    return dyn.detach()
+
+
 def _loss_slabs(hw: int) -> int:
     """Blocks per image of a loss forward: one per 8192 pixels, at most 256."""
     return max(1, min(256, hw // 8192))
@@ -1538,9 +1560,10 @@ BoundaryLossFn.last_out = None
 CONSISTENCY_MAX_CLASSES = 8
 
 
-def _consistency_slabs(hw: int) -> int:
-    """Blocks per image of the consistency forward: one per 2048 pixels (two four-pixel groups per thread), at most 1024.  Finer than
-    `_loss_slabs`: the forward evaluates two soft-maxes in double per pixel, and the unlabelled half of a batch is few images."""
+def _two_logits_slabs(hw: int) -> int:
+    """Blocks per image of the forward of a loss between two logits tensors (consistency, cross pseudo supervision): one per 2048
+    pixels (two four-pixel groups per thread), at most 1024.  Finer than `_loss_slabs`: the forward evaluates two soft-maxes in double
+    per pixel, and the unlabelled half of a batch is few images."""
     return max(1, min(1024, hw // 2048))
 
 
@@ -1555,17 +1578,10 @@ class ConsistencyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, student, teacher, prob_mean, dyn, den_scale: float):
         _need_dev(student, teacher, prob_mean, dyn)
-        if student.ndim != 4:
-            raise NotImplementedError("the HIP consistency loss implements 2-D inputs [B, K, H, W]")
-        if teacher.shape != student.shape:
-            raise MiaError(f"consistency loss: teacher logits {tuple(teacher.shape)} and student logits {tuple(student.shape)} differ")
-        student, st = _loss_logits(student)
-        teacher, tt = _loss_logits(teacher.detach())
+        student, st, teacher, tt = _loss_logits_pair("consistency loss", student, teacher.detach(),
+                                                     "consistency loss: teacher logits {b} and student logits {a} differ")
         b, k1, h, w = student.shape
-        if dyn is not None:
-            if dyn.dtype != torch.float32 or dyn.numel() != 2 or not dyn.is_contiguous():
-                raise MiaError("consistency loss: `dyn` is two contiguous fp32 values {weight, threshold} on the device")
-            dyn = dyn.detach()
+        dyn = _dyn_arg("consistency loss", dyn, 2, True)
         hw = h * w
         dev = student.device
         keep = None
@@ -1577,7 +1593,7 @@ class ConsistencyFn(torch.autograd.Function):
             prob_mean = prob_mean.detach().contiguous()
             if b > 0 and hw > 0:
                 keep = torch.empty((b, h, w), device=dev, dtype=torch.uint8)  # every byte is written by the forward kernel
-        slabs = _consistency_slabs(hw)
+        slabs = _two_logits_slabs(hw)
         words = max(lib().mia_consistency_workspace(b, slabs), 0)  # < 0: a bad shape, reported by the call below
         buf = torch.empty(words + 4, device=dev, dtype=torch.float32)  # workspace | out[3] | coef: one allocation, every word written
         ws, out, coef = buf[:words], buf[words:words + 3], buf[words + 3:]
@@ -1662,10 +1678,7 @@ class PyramidConsistencyFn(torch.autograd.Function):
             if z.shape[0] != b or z.shape[1] != k1 or hh % z.shape[2] or ww % z.shape[3] or hh // z.shape[2] != ww // z.shape[3]:
                 raise MiaError(f"pyramid consistency: output {tuple(z.shape)} against the full-resolution {tuple(logits[0].shape)}")
             factors.append(hh // z.shape[2])
-        if dyn is not None:
-            if dyn.dtype != torch.float32 or dyn.numel() < 1 or not dyn.is_contiguous():
-                raise MiaError("pyramid consistency: `dyn` is a contiguous fp32 device tensor whose first element is the weight")
-            dyn = dyn.detach()
+        dyn = _dyn_arg("pyramid consistency", dyn, 1, False)
         zs, sts = zip(*[_loss_logits(z) for z in logits])
         dev = zs[0].device
         slabs = _urpc_slabs(hh * ww)
@@ -1715,20 +1728,13 @@ class CrossPseudoFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, za, zb, dyn):
         _need_dev(za, zb, dyn)
-        if za.ndim != 4:
-            raise NotImplementedError("the HIP cross pseudo supervision loss implements 2-D inputs [B, K, H, W]")
-        if zb.shape != za.shape:
-            raise MiaError(f"cross pseudo supervision: logits {tuple(za.shape)} and {tuple(zb.shape)} differ")
-        za, sa = _loss_logits(za)
-        zb, sb = _loss_logits(zb)
+        za, sa, zb, sb = _loss_logits_pair("cross pseudo supervision loss", za, zb,
+                                           "cross pseudo supervision: logits {a} and {b} differ")
         b, k1, h, w = za.shape
-        if dyn is not None:
-            if dyn.dtype != torch.float32 or dyn.numel() != 2 or not dyn.is_contiguous():
-                raise MiaError("cross pseudo supervision: `dyn` is two contiguous fp32 values {weight, threshold} on the device")
-            dyn = dyn.detach()
+        dyn = _dyn_arg("cross pseudo supervision", dyn, 2, True)
         hw = h * w
         dev = za.device
-        slabs = _consistency_slabs(hw)
+        slabs = _two_logits_slabs(hw)
         words = max(lib().mia_cps_workspace(b, slabs), 0)  # < 0: a bad shape, reported by the call below
         buf = torch.empty(words + 4, device=dev, dtype=torch.float32)  # workspace | out[4]: one allocation, every word written
         ws, out = buf[:words], buf[words:]

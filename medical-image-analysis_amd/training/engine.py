@@ -298,7 +298,59 @@ class _ReservedCUs:
         return False
 
 
-class TrainEngine:
+class EngineBase:
+    """What every train engine shares (`TrainEngine` here, the semi-supervised engines of training/semi.py): how optimizer and LR
+    schedule are built, the backward seed, the logged loss value, the checkpoint forwarding and the default prediction.  A subclass
+    sets `model`, `optimizer`, `lr_scheduler` and `current_iter`, which `training/checkpoint.py` reads."""
+
+    _one = None  # the reused backward seed
+
+    @staticmethod
+    def _make_optimizer(model, optimizer_name: str, optimizer_kwargs: Optional[dict], start_lr: float, num_iters: int,
+                        lr_warmup_iter: int, lr_interval: int, lr_scheduler_name: str, **flat_kwargs):
+        """(FlatOptimizer, PolyLRScheduler or None) for one network; `flat_kwargs` are FlatOptimizer's own (bucket_bytes)."""
+        optimizer = FlatOptimizer(model, optimizer_name, **flat_kwargs, **dict(optimizer_kwargs or {}))
+        if lr_scheduler_name == "poly":
+            return optimizer, PolyLRScheduler(optimizer, initial_lr=start_lr, max_steps=num_iters, warmup_steps=lr_warmup_iter,
+                                              interval=lr_interval)
+        if lr_scheduler_name == "none":
+            return optimizer, None
+        raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
+
+    def _backward(self, loss: torch.Tensor) -> None:
+        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
+            self._one = torch.ones_like(loss)  # reused d(loss)/d(loss): autograd would launch a fill kernel per step
+        loss.backward(self._one)
+
+    def loss_value(self, loss: torch.Tensor) -> float:
+        """`loss.item()` for logging (al_trainer.py:1381) -- the one host sync of a logged step -- plus the label-range check
+        the reference performs by raising inside the loss (dice_loss.py:25-30)."""
+        v = float(loss.item())
+        ops.check_labels()
+        return v
+
+    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
+        """model.pth (+ training_state.pth) in the reference's layout (al_trainer.py:1719-1733)."""
+        from training import checkpoint
+        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+
+    def load_state_dict(self, save_path) -> dict:
+        """al_trainer.py:1704-1717."""
+        from training import checkpoint
+        return checkpoint.load_state_dict(self, save_path)
+
+    @torch.no_grad()
+    def _predict(self, net, image: torch.Tensor) -> torch.Tensor:
+        net.eval()
+        out = net(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
+        return out.softmax(1).argmax(1)
+
+    def predict(self, image: torch.Tensor) -> torch.Tensor:
+        """valid_slices core (al_trainer.py:1428-1431): eval forward -> softmax -> argmax."""
+        return self._predict(self.model, image)
+
+
+class TrainEngine(EngineBase):
     """One object = model + loss + flat optimizer + poly LR (+ DP reducer).  ``train_step`` returns the loss
     TENSOR (no host sync); call ``.item()`` only when you log."""
 
@@ -361,15 +413,8 @@ class TrainEngine:
                 warnings.warn("TrainEngine: batch-norm model on %d ranks with sync_batchnorm=False -- statistics are per rank, "
                               "results differ from a single process at the global batch size" % world)
         self.loss_fn = loss_fn
-        kw = dict(optimizer_kwargs or {})
-        self.optimizer = FlatOptimizer(model, optimizer_name, bucket_bytes=bucket_bytes, **kw)
-        if lr_scheduler_name == "poly":
-            self.lr_scheduler = PolyLRScheduler(self.optimizer, initial_lr=start_lr, max_steps=num_iters,
-                                                warmup_steps=lr_warmup_iter, interval=lr_interval)
-        elif lr_scheduler_name == "none":
-            self.lr_scheduler = None
-        else:
-            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
+        self.optimizer, self.lr_scheduler = self._make_optimizer(model, optimizer_name, optimizer_kwargs, start_lr, num_iters, lr_warmup_iter,
+                                                                 lr_interval, lr_scheduler_name, bucket_bytes=bucket_bytes)
         self.grad_norm = grad_norm
         self.reducer = GradBucketReducer(self.optimizer, process_group, force=force_reducer)
         self.current_iter = 0
@@ -525,9 +570,7 @@ class TrainEngine:
         loss = self.loss_fn(output, label)
         self.optimizer.zero_grad()
         self.reducer.start_step()
-        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
-            self._one = torch.ones_like(loss)  # reused d(loss)/d(loss): autograd would launch a fill kernel per step
-        loss.backward(self._one)
+        self._backward(loss)
         self.reducer.finish()
         self.optimizer.step(max_grad_norm=self.grad_norm, grad_scale=self.reducer.grad_scale)
         self.current_iter += 1
@@ -560,27 +603,3 @@ class TrainEngine:
         elif self._auto_seen >= 3 and self._auto_votes == 0 or self._eager_steps >= self.AUTO_GIVE_UP:
             self.graph_auto = False
             self._auto_pending = []
-
-    def loss_value(self, loss: torch.Tensor) -> float:
-        """`loss.item()` for logging (al_trainer.py:1381) -- the one host sync of a logged step -- plus the label-range check
-        the reference performs by raising inside the loss (dice_loss.py:25-30)."""
-        v = float(loss.item())
-        ops.check_labels()
-        return v
-
-    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
-        """model.pth (+ training_state.pth) in the reference's layout (al_trainer.py:1719-1733)."""
-        from training import checkpoint
-        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
-
-    def load_state_dict(self, save_path) -> dict:
-        """al_trainer.py:1704-1717."""
-        from training import checkpoint
-        return checkpoint.load_state_dict(self, save_path)
-
-    @torch.no_grad()
-    def predict(self, image: torch.Tensor) -> torch.Tensor:
-        """valid_slices core (al_trainer.py:1428-1431): eval forward -> softmax -> argmax."""
-        self.model.eval()
-        out = self.model(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
-        return out.softmax(1).argmax(1)

@@ -8,7 +8,9 @@ the student's (`ops.ema_update`: ONE pass over `FlatOptimizer.flat_param`).  Wit
 by the entropy of the mean of T stochastic teacher passes (fresh input noise, fresh Dropout2d masks), accumulated by the
 prediction path's `mia_softmax_accum`.
 
-`MeanTeacherEngine` composes `FlatOptimizer`, `PolyLRScheduler` and the loss modules; `TrainEngine` is not involved.
+The three engines of this file derive from `SemiEngine`, which owns what they share on top of `training.engine.EngineBase`: the
+batch convention and its checks, the schedule buffer `dyn` and the skeleton of `train_step`.  An engine adds its networks, its loss
+and what it does after the optimizer step; `TrainEngine` is not involved.
 
 Out of scope:
 * hipGraph capture of this step: it runs eagerly.  The consistency weight and the entropy threshold already live in a device
@@ -36,8 +38,7 @@ import torch
 import torch.distributed as dist
 
 from mia_hip import ops
-from scheduler.lr_scheduler import PolyLRScheduler
-from training.engine import FlatOptimizer
+from training.engine import EngineBase
 
 TEACHER_FILE = "mean_teacher.pth"
 CPS_PEER_FILE = "cps_peer.pth"
@@ -59,7 +60,79 @@ def _ramp_value(r, i: int) -> float:
     return float(r.step(i)) if hasattr(r, "step") else float(r)
 
 
-class MeanTeacherEngine:
+class SemiEngine(EngineBase):
+    """The part of a semi-supervised engine that does not depend on the method.  A batch is {"image": [B,C,H,W], "label":
+    [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones.  `train_step` is the common skeleton; a subclass gives
+    `_loss(image, label)` (forward passes and loss terms; it calls `_write_dyn` before anything reads `dyn`, and only when it forms the
+    unsupervised term), `_dyn_values()` and, where it has them, `_nets()`, `_steppers()` and `_after_step()`.
+
+    `dyn` is the device buffer of the values that follow a schedule, read by the loss kernels when they run: dyn[0] is the weight of
+    the unsupervised term, dyn[1] the method's threshold (unused by URPC)."""
+
+    _one_rank_why = ""
+
+    def __init__(self, model, labeled_bs: int, grad_norm: float, process_group, *optimizer_args):
+        """optimizer_args: (optimizer_name, optimizer_kwargs, start_lr, num_iters, lr_warmup_iter, lr_interval, lr_scheduler_name)."""
+        who = type(self).__name__
+        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
+            raise NotImplementedError(f"{who} runs on one rank{self._one_rank_why}")
+        if labeled_bs < 1:
+            raise ValueError(f"{who}: labeled_bs must be at least 1")
+        self.model = model
+        self.labeled_bs = int(labeled_bs)
+        self._optimizer_args = optimizer_args
+        self.optimizer, self.lr_scheduler = self._make_optimizer(model, *optimizer_args)
+        self.grad_norm = grad_norm
+        self.dyn = torch.zeros(2, device=self.optimizer.flat_param.device, dtype=torch.float32)
+        self.current_iter = 0
+
+    def _nets(self):
+        """The networks `train_step` puts into train mode."""
+        return (self.model,)
+
+    def _steppers(self):
+        """(optimizer, LR scheduler or None) of every trained network, in the order they step."""
+        return ((self.optimizer, self.lr_scheduler),)
+
+    def _after_step(self) -> None:
+        """What follows the optimizer step(s)."""
+
+    def _write_dyn(self) -> None:
+        for slot, v in enumerate(self._dyn_values()):
+            self.dyn[slot].fill_(v)  # a fill launch that carries the value as an argument: no staging copy, no host sync
+
+    def _stage(self, sampled_batch):
+        who = type(self).__name__
+        dev = self.optimizer.flat_param.device
+        lb = self.labeled_bs
+        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
+        label = sampled_batch["label"].to(dev, non_blocking=True)
+        if image.ndim != 4:
+            raise NotImplementedError(f"{who} implements 2-D inputs [B, C, H, W]")
+        if label.shape[0] < lb or image.shape[0] < lb:
+            raise ValueError(f"{who}: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
+        return image, label
+
+    def train_step(self, sampled_batch) -> torch.Tensor:
+        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
+        for net in self._nets():
+            net.train()
+        steppers = self._steppers()
+        for _, sched in steppers:
+            if sched:
+                sched.step(self.current_iter)
+        loss = self._loss(*self._stage(sampled_batch))
+        for opt, _ in steppers:
+            opt.zero_grad()
+        self._backward(loss)
+        for opt, _ in steppers:
+            opt.step(max_grad_norm=self.grad_norm)
+        self._after_step()
+        self.current_iter += 1
+        return loss.detach()
+
+
+class MeanTeacherEngine(SemiEngine):
     """student + EMA teacher + supervised loss + consistency loss + flat optimizer + poly LR.  `train_step` returns the loss TENSOR
     (no host sync); `last_supervised`, `last_consistency` (unweighted) and `last_kept` are device by-products of the latest step.
 
@@ -75,48 +148,37 @@ class MeanTeacherEngine:
     uncertainty_passes: T extra teacher passes whose mean soft-max masks the consistency term; 0 = the plain Mean Teacher form.
     noise_std, noise_clip: the teacher sees `image + clamp(N(0, noise_std^2), -noise_clip, noise_clip)`."""
 
+    _one_rank_why = " (the EMA and the teacher passes are not sharded yet)"
+
     def __init__(self, model, teacher, supervised_loss, labeled_bs: int, ema_decay: float = 0.99, consistency=None,
                  consistency_weight=0.1, uncertainty_passes: int = 0, threshold_ramp=None, noise_std: float = 0.1,
                  noise_clip: float = 0.2, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
                  start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
                  lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
-        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
-            raise NotImplementedError("MeanTeacherEngine runs on one rank (the EMA and the teacher passes are not sharded yet)")
-        if labeled_bs < 1:
-            raise ValueError("MeanTeacherEngine: labeled_bs must be at least 1")
         if not 0.0 <= ema_decay <= 1.0:
             raise ValueError("MeanTeacherEngine: ema_decay must lie in [0, 1]")
         if uncertainty_passes < 0:
             raise ValueError("MeanTeacherEngine: uncertainty_passes must not be negative")
-        self.model, self.teacher = model, teacher
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.teacher = teacher
         self.supervised_loss = supervised_loss
-        self.labeled_bs = int(labeled_bs)
         self.ema_decay = float(ema_decay)
         self.uncertainty_passes = int(uncertainty_passes)
         self.consistency_weight, self.threshold_ramp = consistency_weight, threshold_ramp
         self.noise_std, self.noise_clip = float(noise_std), float(noise_clip)
-        self.optimizer = FlatOptimizer(model, optimizer_name, **dict(optimizer_kwargs or {}))
-        if lr_scheduler_name == "poly":
-            self.lr_scheduler = PolyLRScheduler(self.optimizer, initial_lr=start_lr, max_steps=num_iters,
-                                                warmup_steps=lr_warmup_iter, interval=lr_interval)
-        elif lr_scheduler_name == "none":
-            self.lr_scheduler = None
-        else:
-            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
-        self.grad_norm = grad_norm
         self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
         if consistency is None:
             from losses.consistency_loss import SoftmaxMSEConsistency
             consistency = SoftmaxMSEConsistency(self.num_classes - 1)
         self.consistency = consistency or None
         self._adopt_teacher()
-        dev = self.optimizer.flat_param.device
-        self.dyn = torch.zeros(2, device=dev, dtype=torch.float32)  # {weight, threshold}, read by the kernels when they run
-        self.current_iter = 0
         self.ema_step = 0
         self._teacher_plan = None
-        self._one = None
         self.last_supervised = self.last_consistency = self.last_kept = None
+
+    def _nets(self):
+        return (self.model, self.teacher)
 
     def _adopt_teacher(self) -> None:
         """Teacher parameters -> views into `teacher_flat` at the student's offsets; values and buffers copied from the student."""
@@ -141,11 +203,9 @@ class MeanTeacherEngine:
             t.requires_grad_(False)
         ops.bump_param_epoch()
 
-    def _write_dyn(self) -> None:
-        w = _ramp_value(self.consistency_weight, self.current_iter)
+    def _dyn_values(self):
         r = 0.0 if self.threshold_ramp is None else _ramp_value(self.threshold_ramp, self.current_iter)
-        self.dyn[0].fill_(w)  # two fill launches that carry the values as arguments: no staging copy, no host sync
-        self.dyn[1].fill_(entropy_threshold(r, self.num_classes))
+        return _ramp_value(self.consistency_weight, self.current_iter), entropy_threshold(r, self.num_classes)
 
     def _noisy(self, x: torch.Tensor) -> torch.Tensor:
         if self.noise_std == 0.0:
@@ -166,20 +226,8 @@ class MeanTeacherEngine:
                 softmax_accum(self.teacher(self._noisy(unlabeled)), pbar, None, weight=1.0 / self.uncertainty_passes, first=i == 0)
         return zt, pbar
 
-    def train_step(self, sampled_batch) -> torch.Tensor:
-        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
-        self.model.train()
-        self.teacher.train()
-        if self.lr_scheduler:
-            self.lr_scheduler.step(self.current_iter)
-        dev = self.optimizer.flat_param.device
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
         lb = self.labeled_bs
-        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
-        label = sampled_batch["label"].to(dev, non_blocking=True)
-        if image.ndim != 4:
-            raise NotImplementedError("MeanTeacherEngine implements 2-D inputs [B, C, H, W]")
-        if label.shape[0] < lb or image.shape[0] < lb:
-            raise ValueError(f"MeanTeacherEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
         consistent = self.consistency is not None and image.shape[0] > lb
         if consistent:
             self._write_dyn()
@@ -187,29 +235,19 @@ class MeanTeacherEngine:
         output = self.model(image)
         sup = self.supervised_loss(output[:lb], label[:lb])
         self.last_supervised = sup.detach()
-        if consistent:
-            loss = sup + self.consistency(output[lb:], zt, pbar, dyn=self.dyn)
-            self.last_consistency = getattr(self.consistency, "last_value", None)
-            self.last_kept = getattr(self.consistency, "last_kept", None)
-        else:
-            loss = sup
-        self.optimizer.zero_grad()
-        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
-            self._one = torch.ones_like(loss)
-        loss.backward(self._one)
-        self.optimizer.step(max_grad_norm=self.grad_norm)
-        self.current_iter += 1
-        self._update_teacher()
-        return loss.detach()
+        if not consistent:
+            return sup
+        loss = sup + self.consistency(output[lb:], zt, pbar, dyn=self.dyn)
+        self.last_consistency = getattr(self.consistency, "last_value", None)
+        self.last_kept = getattr(self.consistency, "last_kept", None)
+        return loss
 
-    def _ema(self, alpha: float) -> None:
-        ops.ema_update(self.teacher_flat, self.optimizer.flat_param, alpha)
-
-    def _update_teacher(self) -> None:
+    def _after_step(self) -> None:
         """The EMA over the flat buffers, then the teacher's packed weight copies.  The optimizer step just before has moved the
         parameter epoch on, so every packed copy of a teacher weight made before this point misses on its next use; the plan
-        re-packs them in one launch and marks them current."""
-        self._ema(ema_alpha(self.ema_step, self.ema_decay))
+        re-packs them in one launch and marks them current.  The decay follows `ema_step`, the number of EMA updates done so far,
+        not `current_iter`."""
+        ops.ema_update(self.teacher_flat, self.optimizer.flat_param, ema_alpha(self.ema_step, self.ema_decay))
         self.ema_step += 1
         if self.ema_step < 2 or not self.teacher_flat.is_cuda:
             return
@@ -224,31 +262,20 @@ class MeanTeacherEngine:
             self._teacher_plan = ops.PackPlan(self.teacher_params, dts.pop())
         self._teacher_plan.repack()
 
-    def loss_value(self, loss: torch.Tensor) -> float:
-        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
-        v = float(loss.item())
-        ops.check_labels()
-        return v
-
-    @torch.no_grad()
     def predict(self, image: torch.Tensor, use_teacher: bool = False) -> torch.Tensor:
         """eval forward -> softmax -> argmax, with the student's or the teacher's weights."""
-        net = self.teacher if use_teacher else self.model
-        net.eval()
-        out = net(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
-        return out.softmax(1).argmax(1)
+        return self._predict(self.teacher if use_teacher else self.model, image)
 
     def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
         """The student as `TrainEngine.save_state_dict` writes it (model.pth, training_state.pth on request: the reference's
         layout), plus the teacher's `state_dict` and the EMA step count in a file of their own."""
         from training import checkpoint
-        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+        super().save_state_dict(save_path, save_training_state, **extra)
         torch.save({"teacher": checkpoint.model_state_for_save(self.teacher), "ema_step": int(self.ema_step)},
                    Path(save_path) / TEACHER_FILE)
 
     def load_state_dict(self, save_path) -> dict:
-        from training import checkpoint
-        out = checkpoint.load_state_dict(self, save_path)
+        out = super().load_state_dict(save_path)
         tf = Path(save_path) / TEACHER_FILE
         if tf.is_file():
             sd = torch.load(tf, map_location=self.teacher_flat.device, weights_only=True)
@@ -258,7 +285,7 @@ class MeanTeacherEngine:
         return out
 
 
-class URPCEngine:
+class URPCEngine(SemiEngine):
     """one network + deep-supervised loss on the labelled images + pyramid consistency on the unlabelled ones + flat optimizer + poly
     LR.  `train_step` returns the loss TENSOR (no host sync); `last_supervised` and `last_consistency` (unweighted) are device
     by-products of the latest step.
@@ -275,15 +302,12 @@ class URPCEngine:
                  optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000,
                  lr_warmup_iter: int = 250, lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0,
                  process_group=None):
-        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
-            raise NotImplementedError("URPCEngine runs on one rank")
-        if labeled_bs < 1:
-            raise ValueError("URPCEngine: labeled_bs must be at least 1")
         heads = getattr(getattr(model, "decoder", None), "ds", None)
         if heads is None or all(h is None for h in heads):
             raise ValueError("URPCEngine needs a model whose decoder has auxiliary heads (UNet(deep_supervision=True, ds_layer >= 2)): "
                              "the consistency term compares their outputs")
-        self.model = model
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
         self.num_outputs = 1 + sum(h is not None for h in heads)
         from losses.deep_supervision import DeepSupervisionLoss
         self.supervised_loss = DeepSupervisionLoss(supervised_loss, weights=[1.0 / self.num_outputs] * self.num_outputs)
@@ -291,80 +315,26 @@ class URPCEngine:
             from losses.pyramid_consistency import PyramidConsistencyLoss
             consistency = PyramidConsistencyLoss()
         self.consistency = consistency or None
-        self.labeled_bs = int(labeled_bs)
         self.consistency_weight = consistency_weight
-        self.optimizer = FlatOptimizer(model, optimizer_name, **dict(optimizer_kwargs or {}))
-        if lr_scheduler_name == "poly":
-            self.lr_scheduler = PolyLRScheduler(self.optimizer, initial_lr=start_lr, max_steps=num_iters,
-                                                warmup_steps=lr_warmup_iter, interval=lr_interval)
-        elif lr_scheduler_name == "none":
-            self.lr_scheduler = None
-        else:
-            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
-        self.grad_norm = grad_norm
-        self.dyn = torch.zeros(2, device=self.optimizer.flat_param.device, dtype=torch.float32)  # {weight, unused}: MeanTeacherEngine's layout
-        self.current_iter = 0
-        self._one = None
         self.last_supervised = self.last_consistency = None
 
-    def _write_dyn(self) -> None:
-        self.dyn[0].fill_(_ramp_value(self.consistency_weight, self.current_iter))  # the value travels as a launch argument: no host sync
+    def _dyn_values(self):
+        return (_ramp_value(self.consistency_weight, self.current_iter),)
 
-    def train_step(self, sampled_batch) -> torch.Tensor:
-        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
-        self.model.train()
-        if self.lr_scheduler:
-            self.lr_scheduler.step(self.current_iter)
-        dev = self.optimizer.flat_param.device
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
         lb = self.labeled_bs
-        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
-        label = sampled_batch["label"].to(dev, non_blocking=True)
-        if image.ndim != 4:
-            raise NotImplementedError("URPCEngine implements 2-D inputs [B, C, H, W]")
-        if label.shape[0] < lb or image.shape[0] < lb:
-            raise ValueError(f"URPCEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
         outs = self.model(image, return_ds=True, upsample_ds=False)
         sup = self.supervised_loss([o[:lb] for o in outs], label[:lb])
         self.last_supervised = sup.detach()
-        if self.consistency is not None and image.shape[0] > lb:
-            self._write_dyn()
-            loss = sup + self.consistency([o[lb:] for o in outs], dyn=self.dyn)
-            self.last_consistency = getattr(self.consistency, "last_value", None)
-        else:
-            loss = sup
-        self.optimizer.zero_grad()
-        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
-            self._one = torch.ones_like(loss)
-        loss.backward(self._one)
-        self.optimizer.step(max_grad_norm=self.grad_norm)
-        self.current_iter += 1
-        return loss.detach()
-
-    def loss_value(self, loss: torch.Tensor) -> float:
-        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
-        v = float(loss.item())
-        ops.check_labels()
-        return v
-
-    @torch.no_grad()
-    def predict(self, image: torch.Tensor) -> torch.Tensor:
-        """eval forward (main output only) -> softmax -> argmax."""
-        self.model.eval()
-        out = self.model(image.to(self.optimizer.flat_param.device, dtype=torch.float32))
-        return out.softmax(1).argmax(1)
-
-    def save_state_dict(self, save_path, save_training_state: bool = False, **extra) -> None:
-        """As `TrainEngine.save_state_dict` (model.pth, training_state.pth on request: the reference's layout); there is no second
-        network, hence no file beside them."""
-        from training import checkpoint
-        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
-
-    def load_state_dict(self, save_path) -> dict:
-        from training import checkpoint
-        return checkpoint.load_state_dict(self, save_path)
+        if self.consistency is None or image.shape[0] <= lb:
+            return sup
+        self._write_dyn()  # after the forward here, before the teacher pass in MeanTeacherEngine: what counts is that it precedes the loss
+        loss = sup + self.consistency([o[lb:] for o in outs], dyn=self.dyn)
+        self.last_consistency = getattr(self.consistency, "last_value", None)
+        return loss
 
 
-class CPSEngine:
+class CPSEngine(SemiEngine):
     """two networks + supervised loss on the labelled images for each + cross pseudo supervision between them + two flat optimizers +
     two poly LR schedules.  `train_step` returns the loss TENSOR (no host sync); `last_supervised`, `last_cps` (the unweighted
     LA + LB), `last_agree` (int64: pixels of the CPS slice where the two arg-max labels agree) and `last_confident` (int64 [2]) are
@@ -387,90 +357,54 @@ class CPSEngine:
                  cps_on_labeled: bool = False, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
                  start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
                  lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
-        if dist.is_initialized() and dist.get_world_size(process_group) > 1:
-            raise NotImplementedError("CPSEngine runs on one rank")
-        if labeled_bs < 1:
-            raise ValueError("CPSEngine: labeled_bs must be at least 1")
         if model_a is model_b:
             raise ValueError("CPSEngine needs two networks: model_a and model_b are the same object")
         ka, kb = (int(m.decoder.seg_output.weight.shape[0]) for m in (model_a, model_b))
         if ka != kb:
             raise ValueError(f"CPSEngine: the networks predict {ka} and {kb} classes")
-        if lr_scheduler_name not in ("poly", "none"):
-            raise ValueError(f'Learning rate scheduler "{lr_scheduler_name}" not supported')
-        self.model, self.model_b = model_a, model_b
+        super().__init__(model_a, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.model_b = model_b
+        self.optimizer_b, self.lr_scheduler_b = self._make_optimizer(model_b, *self._optimizer_args)
+        if self.optimizer.flat_param.device != self.optimizer_b.flat_param.device:
+            raise ValueError("CPSEngine: the two networks live on different devices")
         self.supervised_loss = supervised_loss
-        self.labeled_bs = int(labeled_bs)
         self.cps_weight, self.confidence_threshold = cps_weight, confidence_threshold
         self.cps_on_labeled = bool(cps_on_labeled)
         self.num_classes = ka  # K: background included
-        self.optimizer = FlatOptimizer(model_a, optimizer_name, **dict(optimizer_kwargs or {}))
-        self.optimizer_b = FlatOptimizer(model_b, optimizer_name, **dict(optimizer_kwargs or {}))
-        if self.optimizer.flat_param.device != self.optimizer_b.flat_param.device:
-            raise ValueError("CPSEngine: the two networks live on different devices")
-        self.lr_scheduler = self.lr_scheduler_b = None
-        if lr_scheduler_name == "poly":
-            self.lr_scheduler, self.lr_scheduler_b = (PolyLRScheduler(o, initial_lr=start_lr, max_steps=num_iters,
-                                                                      warmup_steps=lr_warmup_iter, interval=lr_interval)
-                                                      for o in (self.optimizer, self.optimizer_b))
-        self.grad_norm = grad_norm
         from losses.cross_pseudo import CrossPseudoSupervisionLoss
         self.cps = CrossPseudoSupervisionLoss(self.num_classes - 1)
-        self.dyn = torch.zeros(2, device=self.optimizer.flat_param.device, dtype=torch.float32)  # {weight, tau}, read by the kernels
-        self.current_iter = 0
-        self._one = None
         self.last_supervised = self.last_cps = self.last_agree = self.last_confident = None
 
-    def _write_dyn(self) -> None:
-        self.dyn[0].fill_(_ramp_value(self.cps_weight, self.current_iter))  # the values travel as launch arguments: no host sync
-        self.dyn[1].fill_(_ramp_value(self.confidence_threshold, self.current_iter))
+    def _nets(self):
+        return (self.model, self.model_b)
 
-    def train_step(self, sampled_batch) -> torch.Tensor:
-        """{"image": [B,C,H,W], "label": [>= labeled_bs, H, W]}: the first `labeled_bs` images are the labelled ones."""
-        self.model.train()
-        self.model_b.train()
-        for sched in (self.lr_scheduler, self.lr_scheduler_b):
-            if sched:
-                sched.step(self.current_iter)
-        dev = self.optimizer.flat_param.device
+    def _steppers(self):
+        return ((self.optimizer, self.lr_scheduler), (self.optimizer_b, self.lr_scheduler_b))
+
+    def _dyn_values(self):
+        return _ramp_value(self.cps_weight, self.current_iter), _ramp_value(self.confidence_threshold, self.current_iter)
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
         lb = self.labeled_bs
-        image = sampled_batch["image"].to(dev, dtype=torch.float32, non_blocking=True)
-        label = sampled_batch["label"].to(dev, non_blocking=True)
-        if image.ndim != 4:
-            raise NotImplementedError("CPSEngine implements 2-D inputs [B, C, H, W]")
-        if label.shape[0] < lb or image.shape[0] < lb:
-            raise ValueError(f"CPSEngine: {label.shape[0]} label maps / {image.shape[0]} images for labeled_bs={lb}")
         out_a = self.model(image)
         out_b = self.model_b(image)
         sup = self.supervised_loss(out_a[:lb], label[:lb]) + self.supervised_loss(out_b[:lb], label[:lb])
         self.last_supervised = sup.detach()
         s = 0 if self.cps_on_labeled else lb
-        if image.shape[0] > s:
-            self._write_dyn()
-            loss = sup + self.cps(out_a[s:], out_b[s:], dyn=self.dyn)
-            self.last_cps = self.cps.last_value_a + self.cps.last_value_b
-            self.last_agree, self.last_confident = self.cps.last_agree, self.cps.last_confident
-        else:
-            loss = sup
-        self.optimizer.zero_grad()
-        self.optimizer_b.zero_grad()
-        if self._one is None or self._one.device != loss.device or self._one.dtype != loss.dtype:
-            self._one = torch.ones_like(loss)
-        loss.backward(self._one)
-        self.optimizer.step(max_grad_norm=self.grad_norm)
-        self.optimizer_b.step(max_grad_norm=self.grad_norm)
+        if image.shape[0] <= s:
+            return sup
+        self._write_dyn()
+        loss = sup + self.cps(out_a[s:], out_b[s:], dyn=self.dyn)
+        self.last_cps = self.cps.last_value_a + self.cps.last_value_b
+        self.last_agree, self.last_confident = self.cps.last_agree, self.cps.last_confident
+        return loss
+
+    def _after_step(self) -> None:
         # B's step moved the parameter epoch on after A's packed weights were rebuilt; A's parameters have not changed since
         plan = self.optimizer._pack_plan
         if plan is not None and plan.valid():
             plan.plant()
-        self.current_iter += 1
-        return loss.detach()
-
-    def loss_value(self, loss: torch.Tensor) -> float:
-        """`loss.item()` for logging plus the label-range check, as `TrainEngine.loss_value`."""
-        v = float(loss.item())
-        ops.check_labels()
-        return v
 
     @torch.no_grad()
     def predict(self, image: torch.Tensor, use: str = "a") -> torch.Tensor:
@@ -478,11 +412,9 @@ class CPSEngine:
         (`inference.predictor.softmax_accum`: ties to the lowest class)."""
         if use not in ("a", "b", "mean"):
             raise ValueError(f'CPSEngine.predict: use="{use}" is none of "a", "b", "mean"')
-        image = image.to(self.optimizer.flat_param.device, dtype=torch.float32)
         if use != "mean":
-            net = self.model if use == "a" else self.model_b
-            net.eval()
-            return net(image).softmax(1).argmax(1)
+            return self._predict(self.model if use == "a" else self.model_b, image)
+        image = image.to(self.optimizer.flat_param.device, dtype=torch.float32)
         from inference.predictor import softmax_accum
         self.model.eval()
         self.model_b.eval()
@@ -497,7 +429,7 @@ class CPSEngine:
         """Network A as `TrainEngine.save_state_dict` writes it (model.pth, training_state.pth on request: the reference's layout);
         network B's `state_dict` -- and on request its optimizer state, in the same torch.optim format -- in a file of its own."""
         from training import checkpoint
-        checkpoint.save_state_dict(self, save_path, save_training_state, **extra)
+        super().save_state_dict(save_path, save_training_state, **extra)
         peer = {"model": checkpoint.model_state_for_save(self.model_b)}
         if save_training_state:
             peer["optimizer"] = checkpoint.optimizer_state_to_torch(self.optimizer_b, self.model_b)
@@ -506,7 +438,7 @@ class CPSEngine:
 
     def load_state_dict(self, save_path) -> dict:
         from training import checkpoint
-        out = checkpoint.load_state_dict(self, save_path)
+        out = super().load_state_dict(save_path)
         pf = Path(save_path) / CPS_PEER_FILE
         if pf.is_file():
             sd = torch.load(pf, map_location=self.optimizer_b.flat_param.device, weights_only=True)

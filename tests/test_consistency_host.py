@@ -219,3 +219,33 @@ def test_mean_teacher_engine_rejects_a_different_teacher():
         MeanTeacherEngine(_tiny(1), UNet(2, 1, 3, [4, 8], normalization="instance"), None, labeled_bs=2)
     with pytest.raises(ValueError):
         MeanTeacherEngine(_tiny(1), _tiny(2), None, labeled_bs=0)
+
+
+def _engine(name, **kw):
+    """One of the three semi-supervised engines on tiny CPU networks."""
+    from models.unet import UNet
+    from training import semi
+    if name == "MeanTeacherEngine":
+        return semi.MeanTeacherEngine(_tiny(1), _tiny(2), None, **kw)
+    if name == "URPCEngine":
+        torch.manual_seed(1)
+        return semi.URPCEngine(UNet(2, 1, 3, [4, 8, 16], deep_supervision=True, ds_layer=2, normalization="instance"), None, **kw)
+    return semi.CPSEngine(_tiny(1), _tiny(2), None, **kw)
+
+
+@pytest.mark.parametrize("name", ["MeanTeacherEngine", "URPCEngine", "CPSEngine"])
+def test_semi_engines_share_one_batch_and_schedule_contract(name):
+    with pytest.raises(ValueError, match=f"{name}: labeled_bs"):
+        _engine(name, labeled_bs=0)
+    with pytest.raises(ValueError, match="not supported"):
+        _engine(name, labeled_bs=2, lr_scheduler_name="cosine")
+    eng = _engine(name, labeled_bs=2, lr_scheduler_name="none")
+    assert eng.lr_scheduler is None
+    if name == "CPSEngine":
+        assert eng.lr_scheduler_b is None
+    assert _engine(name, labeled_bs=2).lr_scheduler is not None
+    with pytest.raises(NotImplementedError, match=f"{name} implements 2-D"):
+        eng.train_step({"image": torch.zeros(4, 1, 16, 16, 16), "label": torch.zeros(2, 16, 16, 16, dtype=torch.long)})
+    with pytest.raises(ValueError, match=f"{name}: 1 label maps / 4 images for labeled_bs=2"):
+        eng.train_step({"image": torch.zeros(4, 1, 16, 16), "label": torch.zeros(1, 16, 16, dtype=torch.long)})
+    assert eng.current_iter == 0

@@ -112,7 +112,7 @@ def main():
         # the kernels alone: preallocated buffers, the entry points called directly
         za, zb = full_a.detach()[lb:], full_b.detach()[lb:]
         sa, sb = ops._pix_strides(za), ops._pix_strides(zb)
-        slabs = ops._consistency_slabs(hw)
+        slabs = ops._two_logits_slabs(hw)
         ws = torch.empty(mia_hip.lib().mia_cps_workspace(nu, slabs), device=dev, dtype=torch.float32)
         out, counts = torch.empty(4, device=dev), torch.empty(3, device=dev, dtype=torch.int64)
         code = torch.empty((nu, h, w), device=dev, dtype=torch.uint8)
