@@ -735,96 +735,111 @@ static bool bwd_vec_ok(const void* dz, const void* y, const void* dy, int dtype,
          ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0;
 }
 
-// pass 1: slab partials of (sum g, sum g*xhat), then per-(n,c) sums parked in c1 / c2
-static void bwd_reduce_launch(const void* dz, const void* dz2, const void* y, int dtype, const float* scale, const float* shift, const float* xa,
-                              const float* xb, int n, int64_t hw, int c, float slope, int slabs, float* partials, float* c1,
-                              float* c2, hipStream_t st, bool do_sum = true) {
-  const bool vec = bwd_vec_ok(dz, y, nullptr, dtype, c);
+// The norm backward's parameter block: every entry point fills one from its C arguments (null / 0 where it has none), bwd_check
+// validates it and the launch helpers read it.  dz2 (optional): second piece of the output gradient, summed on load in fp32 -- a skip
+// tensor's two consumers (unet.py:213, the next encoder level) each deliver their own; needs c % 32 == 0 and 16-byte aligned tensors.
+struct NormBwd {
+  const void *dz, *dz2, *y; void* dy; int dtype;
+  const float *scale, *shift, *xa, *xb, *ysum;
+  int n; int64_t hw; int c, mode, fixed_stats; float slope; int slabs;
+  float *partials, *c1, *c2, *dgamma, *dbeta, *dbias; int accumulate;
+  void* amax_out; hipStream_t st;
+};
+
+extern "C" int mia_norm_two_piece_ok(int dtype, int c) { return (dtype == MIA_BF16 || dtype == MIA_F32) && c % 32 == 0; }
+
+// The null, shape, dtype and two-piece checks of entry point `who`.  tensors: the pointers only this entry has are all there;
+// need_partials / need_grads: it reads (partials, slabs) / writes (dgamma, dbeta).
+static int bwd_check(const char* who, const NormBwd& p, bool tensors, bool need_partials, bool need_grads) {
+  MIA_CHECK_ARG(tensors && p.scale && p.shift && p.xa && p.xb && p.c1 && p.c2 && (!need_partials || p.partials) &&
+                (!need_grads || (p.dgamma && p.dbeta)), "%s: null pointer", who);
+  MIA_CHECK_ARG(p.n > 0 && p.hw > 0 && p.c > 0 && (!need_partials || p.slabs > 0), "%s: bad shape", who);
+  MIA_CHECK_ARG(p.dtype == MIA_BF16 || p.dtype == MIA_F32, "%s: bad dtype", who);
+  MIA_CHECK_ARG(p.dz2 == nullptr || (p.c % 32 == 0 && bwd_vec_ok(p.dz, p.y, p.dy, p.dtype, p.c) && (reinterpret_cast<uintptr_t>(p.dz2) & 15) == 0),
+                "%s: two-piece gradient needs c %% 32 == 0 and aligned tensors", who);
+  return MIA_OK;
+}
+
+// pass 1: slab partials of (sum g, sum g*xhat)
+static void bwd_reduce_launch(const NormBwd& p) {
+  const int n = p.n, c = p.c, slabs = p.slabs;  // (the names the CRV launch macro reads)
+  const int64_t hw = p.hw; float* partials = p.partials; hipStream_t st = p.st;
+  const bool vec = bwd_vec_ok(p.dz, p.y, nullptr, p.dtype, c);
 #define RD(T) hipLaunchKernelGGL(norm_act_bwd_reduce_kernel<T>, dim3(n * slabs, ceil_div(c, 256)), dim3(256), 512 * sizeof(float), st,   \
-                                 static_cast<const T*>(dz), static_cast<const T*>(y), scale, shift, xa, xb, hw, c, slabs, \
-                                 slope, partials)
-  if (vec && c % 32 == 0) {
-    if (dtype == MIA_BF16)
-      CRV(bf16_t, true, static_cast<const bf16_t*>(dz), static_cast<const bf16_t*>(y), static_cast<const bf16_t*>(dz2), scale, shift, xa, xb, slope);
-    else
-      CRV(float, true, static_cast<const float*>(dz), static_cast<const float*>(y), static_cast<const float*>(dz2), scale, shift, xa, xb, slope);
-  } else if (dtype == MIA_BF16) RD(bf16_t); else RD(float);
+                                 static_cast<const T*>(p.dz), static_cast<const T*>(p.y), p.scale, p.shift, p.xa, p.xb, hw, c, slabs, \
+                                 p.slope, partials)
+#define RDV(T) CRV(T, true, static_cast<const T*>(p.dz), static_cast<const T*>(p.y), static_cast<const T*>(p.dz2), p.scale, p.shift, p.xa, p.xb, p.slope)
+  if (vec && c % 32 == 0) { if (p.dtype == MIA_BF16) RDV(bf16_t); else RDV(float); }
+  else if (p.dtype == MIA_BF16) RD(bf16_t); else RD(float);
+#undef RDV
 #undef RD
-  if (do_sum) hipLaunchKernelGGL(norm_bwd_sum_kernel, dim3(n, ceil_div(c, 16)), dim3(256), 0, st, partials, slabs, c, c1, c2);
+}
+
+// Sum (per-(n,c) sums of the slab partials, parked in c1 / c2) unless inline, then finalize (c1, c2 = the group means of g and g*xhat; dgamma, dbeta, dbias).  The partials are the call's own
+// slab partials, whose short sums are folded into the finalize launch; `producer_parts` [n][slabs][c][2] that another kernel left,
+// always summed by their own launch; or none: the sums already sit in c1 / c2 and `group_tot` holds every rank's totals (sync BN).
+static void bwd_finalize_launch(const NormBwd& p, bool producer_parts = false, const float* group_tot = nullptr) {
+  const bool own = !producer_parts && group_tot == nullptr;
+  const bool inline_sums = own && (int64_t)p.n * p.slabs <= 1024;
+  if (group_tot == nullptr && !inline_sums)
+    hipLaunchKernelGGL(norm_bwd_sum_kernel, dim3(p.n, ceil_div(p.c, 16)), dim3(256), 0, p.st, p.partials, p.slabs, p.c, p.c1, p.c2);
+  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(p.c, 16)), dim3(256), 0, p.st, p.n, p.c, p.hw, p.mode, p.fixed_stats,
+                     p.scale, p.xa, p.xb, p.ysum, p.c1, p.c2, p.dgamma, p.dbeta, p.dbias, p.accumulate, group_tot,
+                     inline_sums ? p.partials : nullptr, own ? p.slabs : 0);
 }
 
 // pass 2: dy from the finalized group means
-static void bwd_apply_launch(const void* dz, const void* dz2, const void* y, void* dy, int dtype, const float* scale, const float* shift,
-                             const float* xa, const float* xb, const float* c1, const float* c2, int n, int64_t hw, int c,
-                             float slope, hipStream_t st, void* amax_out = nullptr) {
+static void bwd_apply_launch(const NormBwd& p) {
   // amax_out (fp32 only): max |dy| for the split-f16 convs that consume dy -- folded into the streaming kernel, a separate pass otherwise
-  if (dtype != MIA_F32) amax_out = nullptr;
-  const int epu = dtype == MIA_BF16 ? 8 : 4;
-  const bool vec = bwd_vec_ok(dz, y, dy, dtype, c);
-  const int64_t units = (int64_t)n * hw * (vec ? c / epu : c);
+  void* amax_out = p.dtype == MIA_F32 ? p.amax_out : nullptr;
+  const int epu = p.dtype == MIA_BF16 ? 8 : 4;
+  const bool vec = bwd_vec_ok(p.dz, p.y, p.dy, p.dtype, p.c);
+  const int64_t units = (int64_t)p.n * p.hw * (vec ? p.c / epu : p.c);
   const int blocks = (int)((units + 255) / 256 < 16384 ? (units + 255) / 256 : 16384);
-#define AP(T, V) hipLaunchKernelGGL((norm_act_bwd_apply_kernel<T, V>), dim3(blocks), dim3(256), 0, st,                   \
-                                    static_cast<const T*>(dz), static_cast<const T*>(y), static_cast<T*>(dy), scale, shift, \
-                                    xa, xb, c1, c2, hw, c, units, slope)
+#define AP(T, V) hipLaunchKernelGGL((norm_act_bwd_apply_kernel<T, V>), dim3(blocks), dim3(256), 0, p.st,                   \
+                                    static_cast<const T*>(p.dz), static_cast<const T*>(p.y), static_cast<T*>(p.dy), p.scale, p.shift, \
+                                    p.xa, p.xb, p.c1, p.c2, p.hw, p.c, units, p.slope)
   if (vec) {
     int sl, upb, gy;
-    stream_geometry(n, hw, c, epu, &sl, &upb, &gy);
-#define BS(T, TWOF) hipLaunchKernelGGL((norm_act_bwd_stream_kernel<T, TWOF>), dim3(n * sl, gy), dim3(256), 0, st, static_cast<const T*>(dz), \
-                                       static_cast<const T*>(dz2), static_cast<const T*>(y), static_cast<T*>(dy), scale, shift, xa, xb, \
-                                       c1, c2, hw, c, sl, upb, slope, static_cast<unsigned*>(amax_out))
-    if (dtype == MIA_BF16) { if (dz2) BS(bf16_t, true); else BS(bf16_t, false); }
-    else { if (dz2) BS(float, true); else BS(float, false); }
+    stream_geometry(p.n, p.hw, p.c, epu, &sl, &upb, &gy);
+#define BS(T, TWOF) hipLaunchKernelGGL((norm_act_bwd_stream_kernel<T, TWOF>), dim3(p.n * sl, gy), dim3(256), 0, p.st, static_cast<const T*>(p.dz), \
+                                       static_cast<const T*>(p.dz2), static_cast<const T*>(p.y), static_cast<T*>(p.dy), p.scale, p.shift, p.xa, p.xb, \
+                                       p.c1, p.c2, p.hw, p.c, sl, upb, p.slope, static_cast<unsigned*>(amax_out))
+    if (p.dtype == MIA_BF16) { if (p.dz2) BS(bf16_t, true); else BS(bf16_t, false); }
+    else { if (p.dz2) BS(float, true); else BS(float, false); }
 #undef BS
   } else {
-    if (dtype == MIA_BF16) AP(bf16_t, false);
+    if (p.dtype == MIA_BF16) AP(bf16_t, false);
     else AP(float, false);
-    if (amax_out) (void)mia_amax(static_cast<const float*>(dy), (int64_t)n * hw * c, amax_out, 0, st);
+    if (amax_out) (void)mia_amax(static_cast<const float*>(p.dy), (int64_t)p.n * p.hw * p.c, amax_out, 0, p.st);
   }
 #undef AP
-}
-
-// dz2 (optional): second piece of the output gradient, dz = dz + dz2 summed on load in fp32 -- a skip tensor's two
-// consumers (unet.py:213 and the next encoder level) each deliver their own gradient and no `add` pass is needed.
-// Needs the vectorised path: c % 32 == 0 and 16-byte aligned tensors (mia_norm_two_piece_ok).
-extern "C" int mia_norm_two_piece_ok(int dtype, int c) { return (dtype == MIA_BF16 || dtype == MIA_F32) && c % 32 == 0; }
-static bool two_piece_ok(const void* dz, const void* dz2, const void* y, const void* dy, int dtype, int c) {
-  return dz2 == nullptr || (c % 32 == 0 && bwd_vec_ok(dz, y, dy, dtype, c) && (reinterpret_cast<uintptr_t>(dz2) & 15) == 0);
 }
 
 extern "C" int mia_norm_act_bwd(const void* dz, const void* dz2, const void* y, void* dy, int dtype, const float* scale, const float* shift,
                                 const float* xa, const float* xb, const float* ysum, int n, int64_t hw, int c, int mode,
                                 int fixed_stats, float slope, int slabs, float* partials, float* c1, float* c2, float* dgamma,
                                 float* dbeta, float* dbias, int accumulate, void* amax_out, void* stream) {
-  MIA_CHECK_ARG(dz && y && dy && scale && shift && xa && xb && partials && c1 && c2 && dgamma && dbeta,
-                "mia_norm_act_bwd: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && c > 0 && slabs > 0, "mia_norm_act_bwd: bad shape");
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_act_bwd: bad dtype"); return MIA_EARG; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  MIA_CHECK_ARG(two_piece_ok(dz, dz2, y, dy, dtype, c), "mia_norm_act_bwd: two-piece gradient needs c %% 32 == 0 and aligned tensors");
-  const bool inline_sums = (int64_t)n * slabs <= 1024;  // short slab sums are folded into the finalize launch
-  bwd_reduce_launch(dz, dz2, y, dtype, scale, shift, xa, xb, n, hw, c, slope, slabs, partials, c1, c2, st, !inline_sums);
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, mode, fixed_stats, scale, xa,
-                     xb, ysum, c1, c2, dgamma, dbeta, dbias, accumulate, nullptr, inline_sums ? partials : nullptr, slabs);
-  bwd_apply_launch(dz, dz2, y, dy, dtype, scale, shift, xa, xb, c1, c2, n, hw, c, slope, st, amax_out);
+  const NormBwd p{dz, dz2, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope, slabs, partials, c1, c2,
+                  dgamma, dbeta, dbias, accumulate, amax_out, static_cast<hipStream_t>(stream)};
+  if (int e = bwd_check("mia_norm_act_bwd", p, dz && y && dy, true, true)) return e;
+  bwd_reduce_launch(p);
+  bwd_finalize_launch(p);
+  bwd_apply_launch(p);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
 
-// mia_norm_act_bwd without its apply pass: the reduction over (dz, y) and the finalize (c1, c2 = the group means of g and
-// g*xhat; dgamma, dbeta, dbias) -- for a block whose only consumer of dy forms it on load (mia_stem_wgrad_fused).
+// mia_norm_act_bwd without its apply pass -- for a block whose only consumer of dy forms it on load (mia_stem_wgrad_fused).
 extern "C" int mia_norm_bwd_sums(const void* dz, const void* dz2, const void* y, int dtype, const float* scale, const float* shift,
                                  const float* xa, const float* xb, const float* ysum, int n, int64_t hw, int c, int mode,
                                  int fixed_stats, float slope, int slabs, float* partials, float* c1, float* c2, float* dgamma,
                                  float* dbeta, float* dbias, int accumulate, void* stream) {
-  MIA_CHECK_ARG(dz && y && scale && shift && xa && xb && partials && c1 && c2 && dgamma && dbeta, "mia_norm_bwd_sums: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && c > 0 && slabs > 0, "mia_norm_bwd_sums: bad shape");
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_bwd_sums: bad dtype"); return MIA_EARG; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  MIA_CHECK_ARG(two_piece_ok(dz, dz2, y, nullptr, dtype, c), "mia_norm_bwd_sums: two-piece gradient needs c %% 32 == 0 and aligned tensors");
-  const bool inline_sums = (int64_t)n * slabs <= 1024;
-  bwd_reduce_launch(dz, dz2, y, dtype, scale, shift, xa, xb, n, hw, c, slope, slabs, partials, c1, c2, st, !inline_sums);
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, mode, fixed_stats, scale, xa,
-                     xb, ysum, c1, c2, dgamma, dbeta, dbias, accumulate, nullptr, inline_sums ? partials : nullptr, slabs);
+  const NormBwd p{dz, dz2, y, nullptr, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope, slabs, partials, c1, c2,
+                  dgamma, dbeta, dbias, accumulate, nullptr, static_cast<hipStream_t>(stream)};
+  if (int e = bwd_check("mia_norm_bwd_sums", p, dz && y, true, true)) return e;
+  bwd_reduce_launch(p);
+  bwd_finalize_launch(p);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -836,15 +851,12 @@ extern "C" int mia_norm_act_bwd_pre(const void* dz, const void* y, void* dy, int
                                     const float* xa, const float* xb, const float* ysum, int n, int64_t hw, int c, int mode,
                                     int fixed_stats, float slope, int parts, const float* partials, float* c1, float* c2,
                                     float* dgamma, float* dbeta, float* dbias, int accumulate, void* amax_out, void* stream) {
-  MIA_CHECK_ARG(scale && shift && xa && xb && partials && c1 && c2 && dgamma && dbeta, "mia_norm_act_bwd_pre: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && c > 0 && parts > 0, "mia_norm_act_bwd_pre: bad shape");
+  const NormBwd p{dz, nullptr, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope, parts,
+                  const_cast<float*>(partials), c1, c2, dgamma, dbeta, dbias, accumulate, amax_out, static_cast<hipStream_t>(stream)};
+  if (int e = bwd_check("mia_norm_act_bwd_pre", p, true, true, true)) return e;
   MIA_CHECK_ARG(dy == nullptr || (dz && y), "mia_norm_act_bwd_pre: the apply pass needs dz and y");
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_act_bwd_pre: bad dtype"); return MIA_EARG; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(norm_bwd_sum_kernel, dim3(n, ceil_div(c, 16)), dim3(256), 0, st, partials, parts, c, c1, c2);
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, mode, fixed_stats, scale, xa,
-                     xb, ysum, c1, c2, dgamma, dbeta, dbias, accumulate, nullptr, nullptr, 0);
-  if (dy != nullptr) bwd_apply_launch(dz, nullptr, y, dy, dtype, scale, shift, xa, xb, c1, c2, n, hw, c, slope, st, amax_out);
+  bwd_finalize_launch(p, true);
+  if (dy != nullptr) bwd_apply_launch(p);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -872,13 +884,12 @@ __global__ void bn_bwd_local_tot_kernel(int n_img, int c, int64_t hw, const floa
 extern "C" int mia_norm_act_bwd_reduce(const void* dz, const void* dz2, const void* y, int dtype, const float* scale, const float* shift,
                                        const float* xa, const float* xb, int n, int64_t hw, int c, float slope, int slabs,
                                        float* partials, float* c1, float* c2, float* tot, void* stream) {
-  MIA_CHECK_ARG(dz && y && scale && shift && xa && xb && partials && c1 && c2 && tot, "mia_norm_act_bwd_reduce: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && c > 0 && slabs > 0, "mia_norm_act_bwd_reduce: bad shape");
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_act_bwd_reduce: bad dtype"); return MIA_EARG; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  MIA_CHECK_ARG(two_piece_ok(dz, dz2, y, nullptr, dtype, c), "mia_norm_act_bwd_reduce: two-piece gradient needs c %% 32 == 0 and aligned tensors");
-  bwd_reduce_launch(dz, dz2, y, dtype, scale, shift, xa, xb, n, hw, c, slope, slabs, partials, c1, c2, st);
-  hipLaunchKernelGGL(bn_bwd_local_tot_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, c1, c2, tot);
+  const NormBwd p{dz, dz2, y, nullptr, dtype, scale, shift, xa, xb, nullptr, n, hw, c, NORM_BATCH, 0, slope, slabs, partials, c1, c2,
+                  nullptr, nullptr, nullptr, 0, nullptr, static_cast<hipStream_t>(stream)};
+  if (int e = bwd_check("mia_norm_act_bwd_reduce", p, dz && y && tot, true, false)) return e;
+  bwd_reduce_launch(p);
+  hipLaunchKernelGGL(norm_bwd_sum_kernel, dim3(n, ceil_div(c, 16)), dim3(256), 0, p.st, partials, slabs, c, c1, c2);
+  hipLaunchKernelGGL(bn_bwd_local_tot_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, p.st, n, c, hw, c1, c2, tot);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -887,15 +898,11 @@ extern "C" int mia_norm_act_bwd_apply_sync(const void* dz, const void* dz2, cons
                                            const float* shift, const float* xa, const float* xb, const float* ysum, int n,
                                            int64_t hw, int c, float slope, float* c1, float* c2, const float* group_tot,
                                            float* dgamma, float* dbeta, float* dbias, int accumulate, void* amax_out, void* stream) {
-  MIA_CHECK_ARG(dz && y && dy && scale && shift && xa && xb && c1 && c2 && group_tot && dgamma && dbeta,
-                "mia_norm_act_bwd_apply_sync: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && c > 0, "mia_norm_act_bwd_apply_sync: bad shape");
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_act_bwd_apply_sync: bad dtype"); return MIA_EARG; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, NORM_BATCH, 0, scale, xa, xb,
-                     ysum, c1, c2, dgamma, dbeta, dbias, accumulate, group_tot, nullptr, 0);
-  MIA_CHECK_ARG(two_piece_ok(dz, dz2, y, dy, dtype, c), "mia_norm_act_bwd_apply_sync: two-piece gradient needs c %% 32 == 0 and aligned tensors");
-  bwd_apply_launch(dz, dz2, y, dy, dtype, scale, shift, xa, xb, c1, c2, n, hw, c, slope, st, amax_out);
+  const NormBwd p{dz, dz2, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, NORM_BATCH, 0, slope, 0, nullptr, c1, c2,
+                  dgamma, dbeta, dbias, accumulate, amax_out, static_cast<hipStream_t>(stream)};
+  if (int e = bwd_check("mia_norm_act_bwd_apply_sync", p, dz && y && dy && group_tot, false, true)) return e;
+  bwd_finalize_launch(p, false, group_tot);
+  bwd_apply_launch(p);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -1098,22 +1105,15 @@ __global__ __launch_bounds__(256) void norm_act_bwd_stream_head_kernel(const flo
 
 // mia_norm_act_bwd with dz = W^T dl recomputed on the fly (w: [k1][c] fp32, dl: fp32 logits gradient with element strides
 // gsn / gsk / gsp, pixel-linear).  Contract: c % 32 == 0, 2 <= k1 <= 4, 16-byte aligned y / dy, hw < 2^31.
-static int norm_act_bwd_head_run(const float* dlogits, const float* w, int k1, int64_t gsn, int64_t gsk, int64_t gsp,
-                                 const void* y, void* dy, int dtype, const float* scale, const float* shift, const float* xa,
-                                 const float* xb, const float* ysum, int n, int64_t hw, int c, int mode, int fixed_stats,
-                                 float slope, int slabs, float* partials, float* c1, float* c2, float* dgamma, float* dbeta,
-                                 float* dbias, int accumulate, void* stream, float* wpart, float* dwh, float* dbh, int acc_head,
-                                 void* amax_out) {
-  MIA_CHECK_ARG(dlogits && w && y && dy && scale && shift && xa && xb && partials && c1 && c2 && dgamma && dbeta,
-                "mia_norm_act_bwd_head: null pointer");
-  MIA_CHECK_ARG(n > 0 && hw > 0 && hw < ((int64_t)1 << 31) && c > 0 && slabs > 0 && k1 >= 2 && k1 <= 4 && c % 32 == 0,
-                "mia_norm_act_bwd_head: bad shape (c=%d k1=%d)", c, k1);
-  if (dtype != MIA_BF16 && dtype != MIA_F32) { mia_set_error("mia_norm_act_bwd_head: bad dtype"); return MIA_EARG; }
-  MIA_CHECK_ARG(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0, "mia_norm_act_bwd_head: unaligned");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int epu = dtype == MIA_BF16 ? 8 : 4;
+static int norm_act_bwd_head_run(const char* who, const float* dlogits, const float* w, int k1, int64_t gsn, int64_t gsk, int64_t gsp,
+                                 const NormBwd& p, float* wpart, float* dwh, float* dbh, int acc_head) {
+  if (int e = bwd_check(who, p, dlogits && w && p.y && p.dy, true, true)) return e;
+  MIA_CHECK_ARG(p.hw < ((int64_t)1 << 31) && k1 >= 2 && k1 <= 4 && p.c % 32 == 0, "%s: bad shape (c=%d k1=%d)", who, p.c, k1);
+  MIA_CHECK_ARG(((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.dy)) & 15) == 0, "%s: unaligned", who);
+  const int n = p.n, c = p.c, slabs = p.slabs, dtype = p.dtype, epu = dtype == MIA_BF16 ? 8 : 4;
+  const int64_t hw = p.hw; hipStream_t st = p.st;
 #define CRH(T, K, CGW, HG) hipLaunchKernelGGL((colreduce_head_kernel<T, K, CGW, HG>), dim3(n * slabs, c / CGW), dim3(256), 0, st, dlogits, w, \
-                                              static_cast<const T*>(y), scale, shift, xa, xb, (int)hw, c, slabs, slope, gsn, gsp, gsk, partials, wpart)
+                                              static_cast<const T*>(p.y), p.scale, p.shift, p.xa, p.xb, (int)hw, c, slabs, p.slope, gsn, gsp, gsk, p.partials, wpart)
 #define CRHK(T, CGW, HG) do { if (k1 == 2) CRH(T, 2, CGW, HG); else if (k1 == 3) CRH(T, 3, CGW, HG); else CRH(T, 4, CGW, HG); } while (0)
   if (wpart != nullptr) {  // c == 64 (checked by the caller): the head's weight gradient rides in the same pass
     if (dtype == MIA_BF16) CRHK(bf16_t, 64, true); else CRHK(float, 64, true);
@@ -1123,16 +1123,13 @@ static int norm_act_bwd_head_run(const float* dlogits, const float* w, int k1, i
   else { if (dtype == MIA_BF16) CRHK(bf16_t, 32, false); else CRHK(float, 32, false); }
 #undef CRHK
 #undef CRH
-  const bool inline_sums = (int64_t)n * slabs <= 1024;
-  if (!inline_sums) hipLaunchKernelGGL(norm_bwd_sum_kernel, dim3(n, ceil_div(c, 16)), dim3(256), 0, st, partials, slabs, c, c1, c2);
-  hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(256), 0, st, n, c, hw, mode, fixed_stats, scale, xa,
-                     xb, ysum, c1, c2, dgamma, dbeta, dbias, accumulate, nullptr, inline_sums ? partials : nullptr, slabs);
+  bwd_finalize_launch(p);
   int sl, upb, gy;
   stream_geometry(n, hw, c, epu, &sl, &upb, &gy);
-  if (dtype != MIA_F32) amax_out = nullptr;
+  void* amax_out = dtype == MIA_F32 ? p.amax_out : nullptr;
 #define BSH(T, K) hipLaunchKernelGGL((norm_act_bwd_stream_head_kernel<T, K>), dim3(n * sl, gy), dim3(256), 0, st, dlogits, w, \
-                                     static_cast<const T*>(y), static_cast<T*>(dy), scale, shift, xa, xb, c1, c2, (int)hw, c, sl, upb, \
-                                     slope, gsn, gsp, gsk, static_cast<unsigned*>(amax_out))
+                                     static_cast<const T*>(p.y), static_cast<T*>(p.dy), p.scale, p.shift, p.xa, p.xb, p.c1, p.c2, (int)hw, c, sl, upb, \
+                                     p.slope, gsn, gsp, gsk, static_cast<unsigned*>(amax_out))
 #define BSHK(T) do { if (k1 == 2) BSH(T, 2); else if (k1 == 3) BSH(T, 3); else BSH(T, 4); } while (0)
   if (dtype == MIA_BF16) BSHK(bf16_t); else BSHK(float);
 #undef BSHK
@@ -1146,8 +1143,9 @@ extern "C" int mia_norm_act_bwd_head(const float* dlogits, const float* w, int k
                                      const float* xb, const float* ysum, int n, int64_t hw, int c, int mode, int fixed_stats,
                                      float slope, int slabs, float* partials, float* c1, float* c2, float* dgamma, float* dbeta,
                                      float* dbias, int accumulate, void* amax_out, void* stream) {
-  return norm_act_bwd_head_run(dlogits, w, k1, gsn, gsk, gsp, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope,
-                               slabs, partials, c1, c2, dgamma, dbeta, dbias, accumulate, stream, nullptr, nullptr, nullptr, 0, amax_out);
+  const NormBwd p{nullptr, nullptr, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope, slabs, partials, c1, c2,
+                  dgamma, dbeta, dbias, accumulate, amax_out, static_cast<hipStream_t>(stream)};
+  return norm_act_bwd_head_run("mia_norm_act_bwd_head", dlogits, w, k1, gsn, gsk, gsp, p, nullptr, nullptr, nullptr, 0);
 }
 
 // mia_norm_act_bwd_head + mia_head_norm_wgrad in one reduction pass: the head's dW / db are accumulated by the kernel that computes the
@@ -1163,7 +1161,8 @@ extern "C" int mia_norm_act_bwd_head_w(const float* dlogits, const float* w, int
                                        int accumulate_head, void* amax_out, void* stream) {
   MIA_CHECK_ARG(head_workspace && dw_head && db_head, "mia_norm_act_bwd_head_w: null head-gradient pointer");
   MIA_CHECK_ARG(mia_head_w_supported(dtype, c, k1), "mia_norm_act_bwd_head_w: unsupported shape (c=%d k1=%d)", c, k1);
-  return norm_act_bwd_head_run(dlogits, w, k1, gsn, gsk, gsp, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope,
-                               slabs, partials, c1, c2, dgamma, dbeta, dbias, accumulate, stream, head_workspace, dw_head, db_head,
-                               accumulate_head, amax_out);
+  const NormBwd p{nullptr, nullptr, y, dy, dtype, scale, shift, xa, xb, ysum, n, hw, c, mode, fixed_stats, slope, slabs, partials, c1, c2,
+                  dgamma, dbeta, dbias, accumulate, amax_out, static_cast<hipStream_t>(stream)};
+  return norm_act_bwd_head_run("mia_norm_act_bwd_head_w", dlogits, w, k1, gsn, gsk, gsp, p, head_workspace, dw_head, db_head,
+                               accumulate_head);
 }

@@ -662,6 +662,8 @@ class NormCfg:
         self.running_mean, self.running_var, self.num_batches, self.drop_scale = running_mean, running_var, num_batches, drop_scale
         self.sync = sync  # BatchSync or None
 
+    fixed = property(lambda self: self.mode == NORM_BATCH and not self.training)  # eval batch norm: running statistics, no batch sums
+
 
 class BatchSync:
     """Process group for synchronised batch-norm statistics (one process per GPU)."""
@@ -681,15 +683,19 @@ class BatchSync:
         return t
 
 
-def _norm_finalize(cfg: NormCfg, stats, gamma, beta, n, cout, hw, coefs):
-    """Per-(n,c) coefficients from the conv-epilogue partials; batch statistics cover every rank when cfg.sync is set."""
-    sync = cfg.sync if (cfg.sync is not None and cfg.mode == NORM_BATCH and cfg.training and cfg.sync.world > 1) else None
+def _norm_finalize(ctx, cfg: NormCfg, stats, gamma, beta, y) -> torch.Tensor:
+    """The [5, N, C] per-(n,c) coefficient table (xa, xb, scale, shift, sum_y) of a block with raw conv output y, from the conv-epilogue
+    partials; batch statistics cover every rank when cfg.sync is set, and ctx.sync then keeps the group for backward."""
+    n, h, w, cout = y.shape
+    hw = h * w
+    coefs = torch.empty((5, n, cout), device=y.device, dtype=torch.float32)
+    ctx.sync = sync = cfg.sync if (cfg.sync is not None and cfg.mode == NORM_BATCH and cfg.training and cfg.sync.world > 1) else None
     if sync is None:
         call("mia_norm_finalize", _p(stats), n, 0 if stats is None else stats.shape[1], cout, _c_i64(hw), cfg.mode, int(cfg.training),
              _p(cfg.drop_scale), _p(gamma.detach()), _p(beta.detach()), _c_float(cfg.eps), _c_float(cfg.momentum),
              _p(cfg.running_mean), _p(cfg.running_var), _p(cfg.num_batches), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]),
              _p(coefs[3]), _p(coefs[4]), _stream())
-        return None
+        return coefs
     local = torch.empty((3, cout), device=stats.device, dtype=torch.float32)
     call("mia_bn_sync_local_stats", _p(stats), n, stats.shape[1], cout, _c_i64(hw), _p(cfg.drop_scale), _p(coefs[0]),
          _p(coefs[1]), _p(local), _stream())
@@ -697,7 +703,15 @@ def _norm_finalize(cfg: NormCfg, stats, gamma, beta, n, cout, hw, coefs):
     call("mia_norm_finalize_sync", _p(gathered), sync.world, n, cout, _c_i64(hw), _p(cfg.drop_scale), _p(gamma.detach()),
          _p(beta.detach()), _c_float(cfg.eps), _c_float(cfg.momentum), _p(cfg.running_mean), _p(cfg.running_var),
          _p(cfg.num_batches), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]), _p(coefs[3]), _p(coefs[4]), _stream())
-    return sync
+    return coefs
+
+
+def _norm_act_fwd(y, scale, shift, slope) -> torch.Tensor:
+    """z = lrelu(scale[n,c] * y + shift[n,c]) as a new tensor (`mia_norm_act_fwd`; an fp32 z carries its maximum slot)."""
+    n, h, w, c = y.shape
+    z = torch.empty_like(y)
+    call("mia_norm_act_fwd", _p(y), _p(z), _dt(y), _p(scale), _p(shift), n, _c_i64(h * w), c, _c_float(slope), _p(_amax_new(z)), _stream())
+    return z
 
 
 class LazyAct:
@@ -732,10 +746,7 @@ class LazyMaterializeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, coefs, slope):
-        n, h, w, c = y.shape
-        z = torch.empty_like(y)
-        call("mia_norm_act_fwd", _p(y), _p(z), _dt(y), _p(coefs[2]), _p(coefs[3]), n, _c_i64(h * w), c, _c_float(slope), _p(_amax_new(z)), _stream())
-        return z
+        return _norm_act_fwd(y, coefs[2], coefs[3], slope)
 
     @staticmethod
     def backward(ctx, dz):
@@ -758,6 +769,131 @@ def nl_supported(dtype, cin: int, cout: int, h: int, w: int, train: bool) -> boo
     return (not train) or bool(lib().mia_wgrad_nl_supported(WGRAD_3S1, BF16, cin, cout))
 
 
+class _NormBwd:
+    """Step 1 of a block's backward, the norm backward: the parameter run that every `mia_norm_*bwd*` entry shares (`_run`), the scratch
+    behind it (slab partials `part`; `cc`: per-(n,c) sums, then the group means) and where the parameter gradients go -- the registered
+    slices (`grad_dest`) of `dests` = (gamma, beta, bias) where there are any, rows of a private table otherwise or with dests=None."""
+
+    def __init__(self, y, coefs, mode, fixed, slope, dests=None):
+        self.y, self.coefs, self.mode, self.fixed, self.slope = y, coefs, mode, fixed, slope
+        n, h, w, c = y.shape
+        self.dtype, self.n, self.hw, self.c, self.slabs = _dt(y), n, h * w, c, _slabs_for(h * w)
+        self.part = torch.empty((n, self.slabs, c, 2), device=y.device, dtype=torch.float32)
+        self.cc = torch.empty((2, n, c), device=y.device, dtype=torch.float32)
+        dgb = torch.empty((3, c), device=y.device, dtype=torch.float32)
+        got = (None,) * 3 if dests is None else [grad_dest(p) for p in dests]
+        self.dgamma, self.dbeta, self.dbias = (dgb[i] if g is None else g for i, g in enumerate(got))
+
+    def _run(self, slabs, part):
+        k = self.coefs
+        return (_p(k[2]), _p(k[3]), _p(k[0]), _p(k[1]), _p(None if self.fixed else k[4]), self.n, _c_i64(self.hw), self.c, self.mode,
+                int(self.fixed), _c_float(self.slope), slabs, _p(part), _p(self.cc[0]), _p(self.cc[1]), _p(self.dgamma),
+                _p(self.dbeta), _p(self.dbias), 0)
+
+    def plain(self, dz, dz2, dy) -> None:
+        call("mia_norm_act_bwd", _p(dz), _p(dz2), _p(self.y), _p(dy), self.dtype, *self._run(self.slabs, self.part),
+             _p(_amax_new(dy)), _stream())
+
+    def sums(self, dz, dz2) -> None:
+        """No apply pass: the only consumer of dy forms it on load from `cc` (the fused stem weight gradient)."""
+        call("mia_norm_bwd_sums", _p(dz), _p(dz2), _p(self.y), self.dtype, *self._run(self.slabs, self.part), _stream())
+
+    def pre(self, parts, dz, dy) -> None:
+        """The reduction already ran in the epilogue of the conv that produced dz (`parts`); the apply pass only where dy is wanted."""
+        call("mia_norm_act_bwd_pre", _p(None if dy is None else dz), _p(None if dy is None else self.y), _p(dy), self.dtype,
+             *self._run(parts.shape[1], parts), _p(None if dy is None else _amax_new(dy)), _stream())
+
+    def synced(self, sync: BatchSync, dz, dz2, dy) -> None:
+        """Synchronised batch norm: the group means of g and g*xhat cover every rank's shard."""
+        k, cc = self.coefs, self.cc
+        tot = torch.empty((3, self.c), device=self.y.device, dtype=torch.float32)
+        call("mia_norm_act_bwd_reduce", _p(dz), _p(dz2), _p(self.y), self.dtype, _p(k[2]), _p(k[3]), _p(k[0]), _p(k[1]), self.n,
+             _c_i64(self.hw), self.c, _c_float(self.slope), self.slabs, _p(self.part), _p(cc[0]), _p(cc[1]), _p(tot), _stream())
+        sync.all_reduce_sum(tot)
+        call("mia_norm_act_bwd_apply_sync", _p(dz), _p(dz2), _p(self.y), _p(dy), self.dtype, _p(k[2]), _p(k[3]), _p(k[0]), _p(k[1]),
+             _p(k[4]), self.n, _c_i64(self.hw), self.c, _c_float(self.slope), _p(cc[0]), _p(cc[1]), _p(tot), _p(self.dgamma),
+             _p(self.dbeta), _p(self.dbias), 0, _p(_amax_new(dy)), _stream())
+
+    def run(self, dz, dz2, sync, on_load: bool) -> Optional[torch.Tensor]:
+        """Pick the entry.  Returns dy, or None where the only consumer forms it on load (the stem's weight gradient: it has no input gradient)."""
+        pre = _take_cr(dz) if (dz2 is None and sync is None) else None  # reduction already done by the conv that produced dz
+        dy = None if on_load else torch.empty_like(self.y)
+        if pre is not None:
+            self.pre(pre, dz, dy)
+        elif sync is not None:
+            self.synced(sync, dz, dz2, dy)
+        elif on_load:
+            self.sums(dz, dz2)
+        else:
+            self.plain(dz, dz2, dy)
+        return dy
+
+    def head(self, dl, st, w2, dy, entry="mia_norm_act_bwd_head", extra=()) -> None:
+        """dz = W^T dl recomputed on the fly from the 1x1 head's weights w2 and its logits gradient dl (pixel strides st)."""
+        call(entry, _p(dl), _p(w2), w2.shape[0], _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _p(self.y), _p(dy), self.dtype,
+             *self._run(self.slabs, self.part), *extra, _p(_amax_new(dy)), _stream())
+
+    def head_w(self, dl, st, w2, dy, ws, dwh, dbh) -> None:
+        """`head` whose reduction pass also accumulates the head's own dW / db (one pass over (dl, y))."""
+        self.head(dl, st, w2, dy, "mia_norm_act_bwd_head_w", (_p(ws), _p(dwh), _p(dbh), 0))
+
+
+def _block_wgrad(nb: _NormBwd, x1, x2, weight, stride: int, nl, dy, stem: bool = False, dz=None, dz2=None) -> torch.Tensor:
+    """Step 2 of a block's backward: the conv weight gradient, written to the parameter's registered slice where there is one.  The stem
+    has its own kernels; with dy=None (no apply pass ran: `_NormBwd.sums` / `pre`) its kernel forms dy on load from dz, y and the group means."""
+    cout, cin = weight.shape[:2]
+    y, k = nb.y, nb.coefs
+    if not stem:
+        dw = conv_wgrad(WGRAD_3S2 if stride == 2 else WGRAD_3S1, x1, x2, dy, weight.shape, cout, cin, out=grad_dest(weight), nl=nl)
+    else:
+        if dy is None and dz2 is not None:
+            dz = dz + dz2
+        ws = torch.empty(lib().mia_stem_wgrad_workspace(cout), device=y.device, dtype=torch.float32)
+        dw = grad_dest(weight)
+        if dw is None:
+            dw = torch.empty(weight.shape, device=y.device, dtype=torch.float32)
+        if dy is None:
+            call("mia_stem_wgrad_fused", _p(x1), _dt(x1), _p(dz), _p(y), nb.dtype, _p(k[2]), _p(k[3]), _p(k[0]), _p(k[1]),
+                 _p(nb.cc[0]), _p(nb.cc[1]), _c_float(nb.slope), _p(ws), _p(dw), nb.n, y.shape[1], y.shape[2], cout, 0, _stream())
+        else:
+            call("mia_stem_wgrad", _p(x1), _dt(x1), _p(dy), nb.dtype, _p(ws), _p(dw), nb.n, y.shape[1], y.shape[2], cout, 0, _stream())
+    return dw
+
+
+def _block_dgrad(x1, x2, weight, dy, stride: int, nl, dup_in: bool, need1: bool, need2: bool):
+    """Step 3 of a block's backward, where somebody needs it: (dx1, dx2) from dy.  nl = (coefs, slope): x1 is the previous block's raw output."""
+    dx1 = dx2 = None
+    dtype = _dt(dy)
+    n, ho, wo, cout = dy.shape
+    c1, cin = x1.shape[3], weight.shape[1]
+    wb, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=False)
+    split = c1 if x2 is not None else None
+    other = _take_acc(x1) if (stride == 2 and x2 is None and dup_in) else None
+    if other is not None and lib().mia_conv_acc_supported(CONV_T3S2, dtype, cout, cin):
+        # the other consumer of x1 (a skip tensor) has already written its gradient piece: add ours into it, return none of our own
+        amw = getattr(wb, "_mia_amax", None) if _split_ok(dy, n * ho * wo * cout * cin) else None
+        call("mia_conv_mma_acc", CONV_T3S2, dtype, _p(dy), cout, _p(wb), npad, kpad, 0, _p(other), cin, n, ho, wo,
+             x1.shape[1], x1.shape[2], _p(None if amw is None else amax_slot(dy)), _p(None if amw is None else amw[0]),
+             _p(None if amw is None else getattr(wb, "_mia_split", None)), _stream())
+    elif stride == 2:
+        dx1, dx2, _ = conv_mma(CONV_T3S2, dy, None, wb, npad, kpad, False, None, cin, (x1.shape[1], x1.shape[2]), out_split=split)
+    elif nl is not None and cr_supported(dy.dtype, cin, cout, ho, wo):
+        # x1 is the previous block's raw output: its norm-backward reduction rides in this conv's epilogue
+        dx1, _, partials = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (ho, wo), cr=(x1,) + nl)
+        _hint_cr(dx1, partials)
+    else:
+        # decoder block behind a ConvTranspose2d: dx2 is that layer's output gradient and its per-channel sum is
+        # the transposed conv's bias gradient -- the epilogue statistics deliver it without another pass over dx2
+        want = x2 is not None and need2
+        dx1, dx2, st = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (ho, wo), want_stats=want, out_split=split)
+        if want:
+            sums = colsum(st.view(-1, 2 * cin)).view(cin, 2)[c1:, 0]
+            _hint_colsum(dx2, sums)
+        if x2 is not None and need1 and dup_in:
+            _hint_acc(x1, dx1)  # x1 is the skip tensor: its other consumer may add its gradient piece into dx1
+    return dx1, dx2
+
+
 class PlainBlockFn(torch.autograd.Function):
     """Fused reference PlainBlock (src/models/unet/blocks.py:66-105) on NHWC tensors.
 
@@ -771,7 +907,6 @@ class PlainBlockFn(torch.autograd.Function):
         dup=True returns the output TWICE (two tensors on one storage): a skip tensor has two consumers, and handing
         each its own output makes autograd deliver their gradients separately to backward, which sums them on load inside
         the norm kernels instead of autograd launching an `add` over the full activation."""
-        ctx.dup = dup
         # x1 is one of the two views a `dup=True` block handed out (tagged by the model): exactly one gradient will ever arrive
         # for it, so the two consumers may share one gradient tensor (see _ACC_HINT).  Untagged tensors (e.g. a ResidualBlock's
         # output, whose several gradient pieces autograd itself adds up) never take that path.
@@ -781,16 +916,13 @@ class PlainBlockFn(torch.autograd.Function):
         x1 = x1.contiguous()
         x2 = None if x2 is None else x2.contiguous()
         out_dtype = out_dtype or x1.dtype
-        cout_ = weight.shape[0]
+        cout = weight.shape[0]
         assert not (lazy and dup)
-        ctx.nl = None
         stem = (weight.shape[1] == 1 and x2 is None and stride == 1 and x1.shape[3] == 1 and not x1.requires_grad
-                and cout_ % (8 if out_dtype == torch.bfloat16 else 4) == 0 and cout_ <= 256 and nl_coefs is None)
+                and cout % (8 if out_dtype == torch.bfloat16 else 4) == 0 and cout <= 256 and nl_coefs is None)
         if stem:
             z = PlainBlockFn._stem_forward(ctx, x1, weight, bias, gamma, beta, cfg, out_dtype, slope, lazy)
-            if lazy:
-                return z
-            return (z, _dup_view(z)) if dup else z
+            return (z, _dup_view(z)) if dup else z  # (lazy: z is the (y, coefs) pair, and dup is off)
         if x1.dtype != out_dtype:
             x1 = cast_nhwc(x1, out_dtype)
         if x2 is not None and (x2.shape[:3] != x1.shape[:3] or x2.dtype != x1.dtype):
@@ -798,43 +930,31 @@ class PlainBlockFn(torch.autograd.Function):
             raise RuntimeError(f"Sizes of tensors must match except in dimension 1: {tuple(x1.shape)} vs {tuple(x2.shape)} (NHWC)")
         dtype = _dt(x1)
         n, h, w, c1 = x1.shape
-        cout = weight.shape[0]
         if weight.shape[1] != c1 + (0 if x2 is None else x2.shape[3]):
             raise RuntimeError(f"conv weight expects {weight.shape[1]} input channels, got {c1 + (0 if x2 is None else x2.shape[3])}")
         ho, wo = ((h + 1) // 2, (w + 1) // 2) if stride == 2 else (h, w)
         wp, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=True)
         mode = CONV_G3S2 if stride == 2 else CONV_G3S1
-        fixed = cfg.mode == NORM_BATCH and not cfg.training  # eval batch norm: running statistics, no batch sums needed
         nl = None if nl_coefs is None else (nl_coefs, float(nl_slope))
         if nl is not None and (x2 is not None or stride != 1):
             raise MiaError("normalise-on-load serves one-source stride-1 blocks only")
-        y, _, stats = conv_mma(mode, x1, x2, wp, npad, kpad, False, bias.detach().float(), cout, (ho, wo), want_stats=not fixed,
+        y, _, stats = conv_mma(mode, x1, x2, wp, npad, kpad, False, bias.detach().float(), cout, (ho, wo), want_stats=not cfg.fixed,
                                nl=nl)
-        dev = x1.device
-        coefs = torch.empty((5, n, cout), device=dev, dtype=torch.float32)  # xa, xb, scale, shift, sum_y
-        ctx.sync = _norm_finalize(cfg, stats, gamma, beta, n, cout, ho * wo, coefs)
-        ctx.stride, ctx.mode, ctx.fixed, ctx.stem, ctx.slope = stride, cfg.mode, fixed, False, slope
+        coefs = _norm_finalize(ctx, cfg, stats, gamma, beta, y)
+        ctx.stride, ctx.mode, ctx.fixed, ctx.stem, ctx.slope = stride, cfg.mode, cfg.fixed, False, slope
         ctx.small = (bias, beta)  # identities only (gradient destinations); values are not needed in backward
         ctx.nl_slope = float(nl_slope)
+        ctx.save_for_backward(x1, x2, y, coefs, weight, gamma, nl_coefs)
         if lazy:  # the consumer normalises on load: no apply pass, no activation tensor
-            ctx.save_for_backward(x1, x2, y, coefs, weight, gamma, nl_coefs)
             ctx.mark_non_differentiable(coefs)
             return y, coefs
-        z = torch.empty_like(y)
-        call("mia_norm_act_fwd", _p(y), _p(z), dtype, _p(coefs[2]), _p(coefs[3]), n, _c_i64(ho * wo), cout,
-             _c_float(slope), _p(_amax_new(z)), _stream())
-        ctx.save_for_backward(x1, x2, y, coefs, weight, gamma, nl_coefs)
+        z = _norm_act_fwd(y, coefs[2], coefs[3], slope)
         return (z, _dup_view(z)) if dup else z
 
     @staticmethod
-    def _norm_act(ctx, y, stats, gamma, beta, cfg, n, cout, hw, slope=LRELU_SLOPE):
-        dev = y.device
-        coefs = torch.empty((5, n, cout), device=dev, dtype=torch.float32)  # xa, xb, scale, shift, sum_y
-        ctx.sync = _norm_finalize(cfg, stats, gamma, beta, n, cout, hw, coefs)
-        z = torch.empty_like(y)
-        call("mia_norm_act_fwd", _p(y), _p(z), _dt(y), _p(coefs[2]), _p(coefs[3]), n, _c_i64(hw), cout, _c_float(slope),
-             _p(_amax_new(z)), _stream())
-        return z, coefs
+    def _norm_act(ctx, y, stats, gamma, beta, cfg, slope=LRELU_SLOPE):
+        coefs = _norm_finalize(ctx, cfg, stats, gamma, beta, y)
+        return _norm_act_fwd(y, coefs[2], coefs[3], slope), coefs
 
     @staticmethod
     def _stem_forward(ctx, x1, weight, bias, gamma, beta, cfg, out_dtype, slope, lazy=False):
@@ -847,123 +967,33 @@ class PlainBlockFn(torch.autograd.Function):
         if not w2.is_contiguous():
             w2 = w2.contiguous()
         call("mia_stem_fwd", _p(x1), _dt(x1), _p(w2), _p(bias.detach()), _p(y), _dt(y), _p(stats), n, h, w, cout, _stream())
-        ctx.stride, ctx.mode, ctx.fixed, ctx.stem, ctx.slope = 1, cfg.mode, cfg.mode == NORM_BATCH and not cfg.training, True, slope
+        ctx.stride, ctx.mode, ctx.fixed, ctx.stem, ctx.slope = 1, cfg.mode, cfg.fixed, True, slope
         ctx.small = (bias, beta)
         ctx.nl_slope = LRELU_SLOPE
+        coefs = _norm_finalize(ctx, cfg, stats, gamma, beta, y)
+        ctx.save_for_backward(x1, None, y, coefs, weight, gamma, None)
         if lazy:
-            coefs = torch.empty((5, n, cout), device=dev, dtype=torch.float32)
-            ctx.sync = _norm_finalize(cfg, stats, gamma, beta, n, cout, h * w, coefs)
-            ctx.save_for_backward(x1, None, y, coefs, weight, gamma, None)
             ctx.mark_non_differentiable(coefs)
             return y, coefs
-        z, coefs = PlainBlockFn._norm_act(ctx, y, stats, gamma, beta, cfg, n, cout, h * w, slope)
-        ctx.save_for_backward(x1, None, y, coefs, weight, gamma, None)
-        return z
+        return _norm_act_fwd(y, coefs[2], coefs[3], slope)
 
     @staticmethod
     def backward(ctx, *grads):
         x1, x2, y, coefs, weight, gamma, nl_coefs = ctx.saved_tensors
-        dtype = _dt(y)
-        n, ho, wo, cout = y.shape
         pieces = [g_.contiguous() for g_ in grads if g_ is not None]
         if not pieces:
             return (None,) * 14
         dz, dz2 = pieces[0], (pieces[1] if len(pieces) > 1 else None)
-        if dz2 is not None and not (lib().mia_norm_two_piece_ok(dtype, cout) and dz.data_ptr() % 16 == 0 and dz2.data_ptr() % 16 == 0):
+        if dz2 is not None and not (lib().mia_norm_two_piece_ok(_dt(y), y.shape[3]) and dz.data_ptr() % 16 == 0 and dz2.data_ptr() % 16 == 0):
             dz, dz2 = dz + dz2, None  # shapes outside the vectorised kernels: one explicit sum
-        dev = y.device
-        hw = ho * wo
-        slabs = _slabs_for(hw)
-        part = torch.empty((n, slabs, cout, 2), device=dev, dtype=torch.float32)
-        cc = torch.empty((2, n, cout), device=dev, dtype=torch.float32)
-        dgb = torch.empty((3, cout), device=dev, dtype=torch.float32)
-        bias_p, beta_p = ctx.small
-        dgamma, dbeta, dbias = grad_dest(gamma), grad_dest(beta_p), grad_dest(bias_p)
-        dgamma = dgb[0] if dgamma is None else dgamma
-        dbeta = dgb[1] if dbeta is None else dbeta
-        dbias = dgb[2] if dbias is None else dbias
-        pre = _take_cr(dz) if (dz2 is None and ctx.sync is None) else None  # reduction already done by the conv that produced dz
-        if ctx.stem and ctx.sync is None and FUSE_STEM_BWD:
-            # the stem has no input gradient: its weight gradient is the only consumer of dy and forms it on load -- no apply pass
-            if pre is not None:
-                call("mia_norm_act_bwd_pre", None, None, None, dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-                     _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout, ctx.mode, int(ctx.fixed), _c_float(ctx.slope),
-                     pre.shape[1], _p(pre), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta), _p(dbias), 0, None, _stream())
-            else:
-                call("mia_norm_bwd_sums", _p(dz), _p(dz2), _p(y), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-                     _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout, ctx.mode, int(ctx.fixed), _c_float(ctx.slope), slabs,
-                     _p(part), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta), _p(dbias), 0, _stream())
-            if dz2 is not None:
-                dz = dz + dz2
-            ws = torch.empty(lib().mia_stem_wgrad_workspace(cout), device=dev, dtype=torch.float32)
-            dw = grad_dest(weight)
-            if dw is None:
-                dw = torch.empty(weight.shape, device=dev, dtype=torch.float32)
-            call("mia_stem_wgrad_fused", _p(x1), _dt(x1), _p(dz), _p(y), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-                 _p(cc[0]), _p(cc[1]), _c_float(ctx.slope), _p(ws), _p(dw), n, ho, wo, cout, 0, _stream())
-            return (None, None, dw, dbias, dgamma, dbeta) + (None,) * 8
-        dy = torch.empty_like(y)
-        if pre is not None:
-            call("mia_norm_act_bwd_pre", _p(dz), _p(y), _p(dy), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-                 _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout, ctx.mode, int(ctx.fixed), _c_float(ctx.slope),
-                 pre.shape[1], _p(pre), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta), _p(dbias), 0, _p(_amax_new(dy)), _stream())
-        elif ctx.sync is None:
-            call("mia_norm_act_bwd", _p(dz), _p(dz2), _p(y), _p(dy), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-                 _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout, ctx.mode, int(ctx.fixed), _c_float(ctx.slope), slabs,
-                 _p(part), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta), _p(dbias), 0, _p(_amax_new(dy)), _stream())
-        else:  # synchronised batch norm: the group means of g and g*xhat cover every rank's shard
-            tot = torch.empty((3, cout), device=dev, dtype=torch.float32)
-            call("mia_norm_act_bwd_reduce", _p(dz), _p(dz2), _p(y), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]), n,
-                 _c_i64(hw), cout, _c_float(ctx.slope), slabs, _p(part), _p(cc[0]), _p(cc[1]), _p(tot), _stream())
-            ctx.sync.all_reduce_sum(tot)
-            call("mia_norm_act_bwd_apply_sync", _p(dz), _p(dz2), _p(y), _p(dy), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]),
-                 _p(coefs[1]), _p(coefs[4]), n, _c_i64(hw), cout, _c_float(ctx.slope), _p(cc[0]), _p(cc[1]), _p(tot),
-                 _p(dgamma), _p(dbeta), _p(dbias), 0, _p(_amax_new(dy)), _stream())
-        cin = weight.shape[1]
-        if ctx.stem:
-            ws = torch.empty(lib().mia_stem_wgrad_workspace(cout), device=dev, dtype=torch.float32)
-            dw = grad_dest(weight)
-            if dw is None:
-                dw = torch.empty(weight.shape, device=dev, dtype=torch.float32)
-            call("mia_stem_wgrad", _p(x1), _dt(x1), _p(dy), dtype, _p(ws), _p(dw), n, ho, wo, cout, 0, _stream())
-            return (None, None, dw, dbias, dgamma, dbeta) + (None,) * 8
-        wmode = WGRAD_3S2 if ctx.stride == 2 else WGRAD_3S1
-        dw = conv_wgrad(wmode, x1, x2, dy, weight.shape, cout, cin, out=grad_dest(weight),
-                        nl=None if nl_coefs is None else (nl_coefs, ctx.nl_slope))
+        nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope, (gamma, ctx.small[1], ctx.small[0]))
+        dy = nb.run(dz, dz2, ctx.sync, ctx.stem and ctx.sync is None and FUSE_STEM_BWD)
+        nl = None if nl_coefs is None else (nl_coefs, ctx.nl_slope)
+        dw = _block_wgrad(nb, x1, x2, weight, ctx.stride, nl, dy, ctx.stem, dz, dz2)
         dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
-            wb, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=False)
-            c1 = x1.shape[3]
-            split = c1 if x2 is not None else None
-            if ctx.stride == 2:
-                other = _take_acc(x1) if (x2 is None and ctx.dup_in) else None
-                if other is not None and lib().mia_conv_acc_supported(CONV_T3S2, dtype, cout, cin):
-                    # the other consumer of x1 (a skip tensor) has already written its gradient piece: add ours into it
-                    amw = getattr(wb, "_mia_amax", None) if _split_ok(dy, n * ho * wo * cout * cin) else None
-                    call("mia_conv_mma_acc", CONV_T3S2, dtype, _p(dy), cout, _p(wb), npad, kpad, 0, _p(other), cin, n, ho, wo,
-                         x1.shape[1], x1.shape[2], _p(None if amw is None else amax_slot(dy)), _p(None if amw is None else amw[0]),
-                         _p(None if amw is None else getattr(wb, "_mia_split", None)), _stream())
-                    return (None, None, dw, dbias, dgamma, dbeta) + (None,) * 8
-                dx1, dx2, _ = conv_mma(CONV_T3S2, dy, None, wb, npad, kpad, False, None, cin, (x1.shape[1], x1.shape[2]),
-                                       out_split=split)
-            else:
-                # decoder block behind a ConvTranspose2d: dx2 is that layer's output gradient and its per-channel sum is
-                # the transposed conv's bias gradient -- the epilogue statistics deliver it without another pass over dx2
-                want = x2 is not None and ctx.needs_input_grad[1]
-                if nl_coefs is not None and cr_supported(y.dtype, cin, cout, ho, wo):
-                    # x1 is the previous block's raw output: its norm-backward reduction rides in this conv's epilogue
-                    dx1, _, partials = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (ho, wo),
-                                                cr=(x1, nl_coefs, ctx.nl_slope))
-                    _hint_cr(dx1, partials)
-                    return (dx1, None, dw, dbias, dgamma, dbeta) + (None,) * 8
-                dx1, dx2, st = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (ho, wo), want_stats=want,
-                                        out_split=split)
-                if want:
-                    sums = colsum(st.view(-1, 2 * cin)).view(cin, 2)[c1:, 0]
-                    _hint_colsum(dx2, sums)
-                if x2 is not None and ctx.needs_input_grad[0] and ctx.dup_in:
-                    _hint_acc(x1, dx1)  # x1 is the skip tensor: its other consumer may add its gradient piece into dx1
-        return (dx1, dx2, dw, dbias, dgamma, dbeta) + (None,) * 8
+        if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):  # (never the stem: its input needs no gradient)
+            dx1, dx2 = _block_dgrad(x1, x2, weight, dy, ctx.stride, nl, ctx.dup_in, *ctx.needs_input_grad[:2])
+        return (dx1, dx2, dw, nb.dbias, nb.dgamma, nb.dbeta) + (None,) * 8
 
 
 class PlainBlockHeadFn(torch.autograd.Function):
@@ -995,18 +1025,16 @@ class PlainBlockHeadFn(torch.autograd.Function):
         if weight.shape[1] != c1:
             raise RuntimeError(f"conv weight expects {weight.shape[1]} input channels, got {c1}")
         wp, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=True)
-        fixed = cfg.mode == NORM_BATCH and not cfg.training
-        y, _, stats = conv_mma(CONV_G3S1, x1, None, wp, npad, kpad, False, bias.detach().float(), cout, (h, w), want_stats=not fixed,
+        y, _, stats = conv_mma(CONV_G3S1, x1, None, wp, npad, kpad, False, bias.detach().float(), cout, (h, w), want_stats=not cfg.fixed,
                                nl=None if nl_coefs is None else (nl_coefs, float(nl_slope)))
-        coefs = torch.empty((5, n, cout), device=x1.device, dtype=torch.float32)  # xa, xb, scale, shift, sum_y
-        ctx.sync = _norm_finalize(cfg, stats, gamma, beta, n, cout, h * w, coefs)
+        coefs = _norm_finalize(ctx, cfg, stats, gamma, beta, y)
         ctx.nl_slope = float(nl_slope)
         w2 = head_w.detach().reshape(k1, cout).contiguous()
         logits = torch.empty((n, h, w, k1), device=x1.device, dtype=torch.float32)
         call("mia_head_norm_fwd", _p(y), dtype, _p(coefs[2]), _p(coefs[3]), _c_float(slope), _p(w2), _p(head_b.detach()),
              _p(logits), n, _c_i64(h * w), cout, k1, _c_i64(h * w * k1), _c_i64(1), _c_i64(k1), _stream())
         ctx.save_for_backward(x1, y, coefs, weight, gamma, head_w, nl_coefs)
-        ctx.mode, ctx.fixed, ctx.slope = cfg.mode, cfg.mode == NORM_BATCH and not cfg.training, slope
+        ctx.mode, ctx.fixed, ctx.slope = cfg.mode, cfg.fixed, slope
         ctx.small = (bias, beta, head_b)
         return logits.permute(0, 3, 1, 2)
 
@@ -1014,9 +1042,8 @@ class PlainBlockHeadFn(torch.autograd.Function):
     def backward(ctx, dl):
         x1, y, coefs, weight, gamma, head_w, nl_coefs = ctx.saved_tensors
         bias_p, beta_p, head_b = ctx.small
-        dtype = _dt(y)
         n, h, w, cout = y.shape
-        k1, cin = head_w.shape[0], weight.shape[1]
+        k1 = head_w.shape[0]
         dev, hw = y.device, h * w
         if dl.dtype != torch.float32:
             dl = dl.float()
@@ -1025,49 +1052,28 @@ class PlainBlockHeadFn(torch.autograd.Function):
             dl = dl.contiguous()
             st = _pix_strides(dl)
         w2 = head_w.detach().reshape(k1, cout).contiguous()
-        # head parameters
         dwh, dbh = grad_dest(head_w), grad_dest(head_b)
         dwh = torch.empty((k1, cout), device=dev, dtype=torch.float32) if dwh is None else dwh
         dbh = torch.empty(k1, device=dev, dtype=torch.float32) if dbh is None else dbh
-        slabs = _slabs_for(hw)
-        part = torch.empty((n, slabs, cout, 2), device=dev, dtype=torch.float32)
-        cc = torch.empty((2, n, cout), device=dev, dtype=torch.float32)
-        dgb = torch.empty((3, cout), device=dev, dtype=torch.float32)
-        dgamma, dbeta, dbias = grad_dest(gamma), grad_dest(beta_p), grad_dest(bias_p)
-        dgamma = dgb[0] if dgamma is None else dgamma
-        dbeta = dgb[1] if dbeta is None else dbeta
-        dbias = dgb[2] if dbias is None else dbias
+        nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope, (gamma, beta_p, bias_p))
         dy = torch.empty_like(y)
-        if FUSE_HEAD_W and lib().mia_head_w_supported(dtype, cout, k1):
+        if FUSE_HEAD_W and lib().mia_head_w_supported(nb.dtype, cout, k1):
             # head dW / db and the block's norm-backward sums in ONE pass over (dl, y); then the apply pass with dz = W^T dl recomputed
-            ws = torch.empty(n * slabs * k1 * (cout + 1), device=dev, dtype=torch.float32)
-            call("mia_norm_act_bwd_head_w", _p(dl), _p(w2), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _p(y), _p(dy), dtype,
-                 _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]), _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout,
-                 ctx.mode, int(ctx.fixed), _c_float(ctx.slope), slabs, _p(part), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta),
-                 _p(dbias), 0, _p(ws), _p(dwh), _p(dbh), 0, _p(_amax_new(dy)), _stream())
+            ws = torch.empty(n * nb.slabs * k1 * (cout + 1), device=dev, dtype=torch.float32)
+            nb.head_w(dl, st, w2, dy, ws, dwh, dbh)
         else:
             ws = torch.empty(lib().mia_head_bwd_workspace(cout, k1), device=dev, dtype=torch.float32)
-            call("mia_head_norm_wgrad", _p(dl), _p(y), dtype, _p(coefs[2]), _p(coefs[3]), _c_float(ctx.slope), _p(dwh), _p(dbh),
+            call("mia_head_norm_wgrad", _p(dl), _p(y), nb.dtype, _p(coefs[2]), _p(coefs[3]), _c_float(ctx.slope), _p(dwh), _p(dbh),
                  _p(ws), n, _c_i64(hw), cout, k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), 0, _stream())
-            # norm backward with dz = W^T dl recomputed
-            call("mia_norm_act_bwd_head", _p(dl), _p(w2), k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), _p(y), _p(dy), dtype,
-                 _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]), _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout,
-                 ctx.mode, int(ctx.fixed), _c_float(ctx.slope), slabs, _p(part), _p(cc[0]), _p(cc[1]), _p(dgamma), _p(dbeta),
-                 _p(dbias), 0, _p(_amax_new(dy)), _stream())
-        dw = conv_wgrad(WGRAD_3S1, x1, None, dy, weight.shape, cout, cin, out=grad_dest(weight),
-                        nl=None if nl_coefs is None else (nl_coefs, ctx.nl_slope))
+            nb.head(dl, st, w2, dy)
+        nl = None if nl_coefs is None else (nl_coefs, ctx.nl_slope)
+        dw = _block_wgrad(nb, x1, None, weight, 1, nl, dy)
         dx1 = None
         if ctx.needs_input_grad[0]:
-            wb, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=False)
-            if nl_coefs is not None and cr_supported(y.dtype, cin, cout, h, w):
-                dx1, _, partials = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (h, w), cr=(x1, nl_coefs, ctx.nl_slope))
-                _hint_cr(dx1, partials)
-            else:
-                dx1, _, _ = conv_mma(CONV_G3S1, dy, None, wb, npad, kpad, True, None, cin, (h, w))
-        return dx1, dw, dbias, dgamma, dbeta, None, dwh.reshape(head_w.shape), dbh, None, None, None
+            dx1, _ = _block_dgrad(x1, None, weight, dy, 1, nl, False, True, False)
+        return dx1, dw, nb.dbias, nb.dgamma, nb.dbeta, None, dwh.reshape(head_w.shape), dbh, None, None, None
 
 
-# ------------------------------------------------------------------ ConvTranspose2d(k=2, s=2)
 class ConvTranspose2x2Fn(torch.autograd.Function):
     """nn.ConvTranspose2d(cin, cout, 2, 2) (src/models/unet/unet.py:142) as a pointwise MFMA GEMM + pixel shuffle."""
 
@@ -1932,9 +1938,9 @@ class PointwiseNormFn(torch.autograd.Function):
         wp, npad, kpad = PackCache().get(w4, dtype, n_from_d0=True)
         y, _, stats = conv_mma(CONV_G2S2 if stride == 2 else CONV_G1, x, None, wp, npad, kpad, False, bias.detach().float(), cout,
                                (ho, wo), want_stats=True)
-        z, coefs = PlainBlockFn._norm_act(ctx, y, stats, gamma, beta, cfg, n, cout, ho * wo, 1.0)
+        z, coefs = PlainBlockFn._norm_act(ctx, y, stats, gamma, beta, cfg, 1.0)
         ctx.save_for_backward(x, y, coefs, weight, gamma)
-        ctx.stride, ctx.mode, ctx.fixed = stride, cfg.mode, cfg.mode == NORM_BATCH and not cfg.training
+        ctx.stride, ctx.mode, ctx.fixed = stride, cfg.mode, cfg.fixed
         return z
 
     @staticmethod
@@ -1953,16 +1959,9 @@ class PointwiseNormFn(torch.autograd.Function):
         dtype = _dt(y)
         n, ho, wo, cout = y.shape
         cin = weight.shape[1]
-        dev = y.device
-        hw = ho * wo
-        slabs = _slabs_for(hw)
-        part = torch.empty((n, slabs, cout, 2), device=dev, dtype=torch.float32)
-        cc = torch.empty((2, n, cout), device=dev, dtype=torch.float32)
-        dgb = torch.empty((3, cout), device=dev, dtype=torch.float32)
+        nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, 1.0)  # parameter gradients in private rows (this node registers no destinations)
         dy = torch.empty_like(y)
-        call("mia_norm_act_bwd", _p(dz), None, _p(y), _p(dy), dtype, _p(coefs[2]), _p(coefs[3]), _p(coefs[0]), _p(coefs[1]),
-             _p(None if ctx.fixed else coefs[4]), n, _c_i64(hw), cout, ctx.mode, int(ctx.fixed), _c_float(1.0), slabs, _p(part),
-             _p(cc[0]), _p(cc[1]), _p(dgb[0]), _p(dgb[1]), _p(dgb[2]), 0, _p(_amax_new(dy)), _stream())
+        nb.plain(dz, None, dy)
         w4 = PointwiseNormFn._as_taps(weight, ctx.stride)
         if ctx.stride == 2:
             g4 = conv_wgrad(WGRAD_2S2, x, None, dy, w4.shape, cout, cin)
@@ -1977,7 +1976,7 @@ class PointwiseNormFn(torch.autograd.Function):
                 dx, _, _ = conv_mma(CONV_T2S2, dy, None, wb, npad, kpad, False, None, cin, (x.shape[1], x.shape[2]))
             else:
                 dx, _, _ = conv_mma(CONV_G1, dy, None, wb, npad, kpad, False, None, cin, (ho, wo))
-        return dx, dw, dgb[2], dgb[0], dgb[1], None, None
+        return dx, dw, nb.dbias, nb.dgamma, nb.dbeta, None, None
 
 
 class ScaleLReLUFn(torch.autograd.Function):
@@ -1994,8 +1993,7 @@ class ScaleLReLUFn(torch.autograd.Function):
             coef[0].fill_(1.0)
         else:
             coef[0].copy_(m)
-        z = torch.empty_like(v)
-        call("mia_norm_act_fwd", _p(v), _p(z), _dt(v), _p(coef[0]), _p(coef[1]), n, _c_i64(h * w), c, _c_float(slope), _p(_amax_new(z)), _stream())
+        z = _norm_act_fwd(v, coef[0], coef[1], slope)
         ctx.save_for_backward(v, coef)
         ctx.slope = slope
         return z
