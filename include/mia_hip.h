@@ -115,7 +115,8 @@ int mia_get_option(const char* name, int* value);
  * (unet.py:213) is eliminated; out1|out2 are split along channels (o1 + o2) for its gradient.
  * stat_partials (optional): [N][tiles][o1+o2][2] per-tile sum / sum-of-squares of the output
  * (feeds mia_norm_finalize; replaces the statistics pass of InstanceNorm2d/BatchNorm2d, blocks.py:98).
- * tiles = tiles_y * tiles_x from mia_conv_mma_tiles(). */
+ * tiles = tiles_y * tiles_x from mia_conv_mma_tiles().  Gather modes only: MIA_EARG with MIA_CONV_T3S2 / MIA_CONV_T2S2, whose four
+ * parity classes share one entry per tile. */
 int mia_conv_mma_tiles(int mode, int hout, int wout, int* tiles_y, int* tiles_x, int* tile_h);
 /* amax_in1 / amax_in2 / amax_w (optional, fp32 tensors only): device pointers to max |x| of in1 / in2 / the weight tensor as fp32
  * bit patterns (mia_amax / mia_amax_batch).  All present (amax_in2 only when c2 > 0) and option f32_split on: the products run on the
@@ -126,6 +127,24 @@ int mia_conv_mma(int mode, int dtype, const void* in1, int c1, const void* in2, 
                  int kpad, int flip_taps, const float* bias, void* out1, int o1, void* out2, int o2,
                  float* stat_partials, int n, int hin, int win, int hout, int wout, const void* amax_in1, const void* amax_in2,
                  const void* amax_w, const void* wpack_split, void* amax_out1, void* amax_out2, void* stream);
+/* Which kernel family mia_conv_mma (variant 0), mia_conv_mma_nl (1) or mia_conv_mma_acc (2) launches for a shape, under the options
+ * as they are at the call: the launch path and this query share one selection function, and the query launches nothing.  OR
+ * MIA_CONV_VAR_STATS into `variant` for a launch with stat_partials, MIA_CONV_VAR_BIAS for one with a bias (two kernels' contracts
+ * read them).  split != 0: the fp32 operand maxima are passed.  Assumes 16-byte aligned tensors of one image (no 2^31-byte limit
+ * reached).  Returns MIA_CONV_FAM_*, or a negative error code for a shape the variant rejects. */
+#define MIA_CONV_FAM_GENERIC 0    /* conv_mma_kernel: any shape */
+#define MIA_CONV_FAM_FAST 1       /* conv_mma_fast: the branch-free tile kernel */
+#define MIA_CONV_FAM_S2_WIDE 2    /* conv_mma_fast on 512-thread workgroups / 16-row tiles (option conv_s2_wide) */
+#define MIA_CONV_FAM_CONV64 3     /* conv64_persist_kernel */
+#define MIA_CONV_FAM_CONV64_DMA 4 /* conv64_dma_kernel */
+#define MIA_CONV_FAM_CONV_BT 5    /* conv_bt_kernel */
+#define MIA_CONV_FAM_CONV_PW 6    /* conv_pw_kernel */
+#define MIA_CONV_FAM_NL 7         /* conv64_persist_kernel, normalise-on-load */
+#define MIA_CONV_FAM_ACC 8        /* conv_mma_fast, out += result */
+#define MIA_CONV_VAR_STATS 4
+#define MIA_CONV_VAR_BIAS 8
+int mia_conv_mma_family(int mode, int dtype, int c1, int c2, int o1, int o2, int npad, int kpad, int hout, int wout, int variant,
+                        int split);
 /* wpack_split (optional, with the maxima): the packed weights already split into (h | l << 16) fp16 words of w * 2^e (e from amax_w's
  * slot) by mia_split_f16_batch -- same [tap][npad][kpad] layout, 4 bytes per weight; the split kernels then stage them as they are instead
  * of splitting them once per tile.  Device table of `count` {const float* src; void* dst; int64_t n; const void* amax;} records
@@ -212,6 +231,20 @@ int mia_wgrad_geometry(int mode, int dtype, int hy, int wy, int* tiles_y, int* t
  * source, or the 96-wide blocks of 3x3 stride-1 bf16 layers whose channel counts are multiples of 96 and not of 64 (768 threads, one
  * block where the 64-wide form needs 2 x 2).  Supersedes the two queries above for callers that know the channel counts. */
 int mia_wgrad_plan(int mode, int dtype, int c1, int c2, int cdy, int npad, int hy, int* column_blocks, int* target_blocks, int* tile_h);
+/* Which kernel family mia_conv_wgrad (variant 0) or mia_conv_wgrad_nl (1) launches for a shape, under the options as they are at the
+ * call (one selection function shared with the launch path; nothing is launched; 16-byte aligned tensors below 2^31 bytes per image
+ * assumed; `split` as for mia_conv_mma_family -- the split product form runs inside the fp32 families).  Returns MIA_WGRAD_FAM_*, or a
+ * negative error code for a shape the variant rejects. */
+#define MIA_WGRAD_FAM_DMA96 0      /* wgrad_bf16_dma96_kernel */
+#define MIA_WGRAD_FAM_BT 1         /* wgrad_bf16_bt_kernel / _s2 / _t2 */
+#define MIA_WGRAD_FAM_DMA 2        /* wgrad_bf16_dma_kernel */
+#define MIA_WGRAD_FAM_2WG 3        /* wgrad_bf16_2wg_kernel */
+#define MIA_WGRAD_FAM_2WG_NL 4     /* wgrad_bf16_2wg_kernel, normalise-on-load */
+#define MIA_WGRAD_FAM_TILE_FAST 5  /* wgrad_bf16_fast_kernel */
+#define MIA_WGRAD_FAM_F32_FAST 6   /* wgrad_f32_fast_kernel (exact fp32 or split-f16 products) */
+#define MIA_WGRAD_FAM_F32_NARROW 7 /* wgrad_f32_fast_kernel on half-width blocks (every channel count <= 32) */
+#define MIA_WGRAD_FAM_GENERIC 8    /* wgrad_bf16_kernel / wgrad_f32_kernel: any shape */
+int mia_wgrad_family(int mode, int dtype, int c1, int c2, int cdy, int npad, int variant, int split);
 int mia_conv_wgrad(int mode, int dtype, const void* x1, int c1, const void* x2, int c2, const void* dy, int cdy,
                    float* slabs, int ksplit, int npad, int kpad, int n, int hx, int wx, int hy, int wy, const void* amax_x1,
                    const void* amax_x2, const void* amax_dy, void* stream); /* amax_*: as for mia_conv_mma */

@@ -3,6 +3,10 @@
 #include "common.h"
 
 enum { MODE_G3S1 = 0, MODE_G3S2 = 1, MODE_G2S2 = 2, MODE_T3S2 = 3, MODE_T2S2 = 4, MODE_G1 = 5 };
+// kernel families of the dispatcher (conv_mma.hip conv_select; the values of include/mia_hip.h MIA_CONV_FAM_* / MIA_CONV_VAR_*)
+enum { MIA_CONV_FAM_GENERIC = 0, MIA_CONV_FAM_FAST = 1, MIA_CONV_FAM_S2_WIDE = 2, MIA_CONV_FAM_CONV64 = 3, MIA_CONV_FAM_CONV64_DMA = 4,
+       MIA_CONV_FAM_CONV_BT = 5, MIA_CONV_FAM_CONV_PW = 6, MIA_CONV_FAM_NL = 7, MIA_CONV_FAM_ACC = 8 };
+enum { MIA_CONV_VAR_STATS = 4, MIA_CONV_VAR_BIAS = 8 };
 
 struct ConvArgs {
   const void* in1; const void* in2; int c1; int c2;

@@ -307,6 +307,89 @@ extern "C" int mia_conv_mma_tiles(int mode, int hout, int wout, int* tiles_y, in
   return MIA_OK;
 }
 
+// Which kernel family serves a launch, and on what geometry: ONE pure function of the options snapshot and the launch description, shared
+// by the launch path (conv_mma_run switches on its result) and by the query mia_conv_mma_family.  Fills a's tile grid / vector flags.
+struct ConvPlan { int family, mt, nt, grid_y; };
+static ConvPlan conv_select(const MiaOptions& opt, int mode, int dtype, ConvArgs& a) {
+  const int epu = dtype == MIA_BF16 ? 8 : 4;
+  const int c1 = a.c1, c2 = a.c2, o1 = a.o1, o2 = a.o2, hout = a.Hout;
+  int th;
+  conv_tiles(opt, mode, hout, a.Wout, &a.tiles_y, &a.tiles_x, &th);
+  int mt = th / 4;
+  const int nout = o1 + o2;
+  const int nt = nout > 32 ? 4 : (nout > 16 ? 2 : 1);
+  a.nblk_n = ceil_div(nout, 16 * nt);
+  a.st_tiles_y = a.tiles_y;
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  a.vec_in = (c1 % epu == 0) && (c2 % epu == 0) && al16(a.in1) && (a.in2 == nullptr || al16(a.in2));
+  a.vec_out = (o1 % epu == 0) && (o2 % epu == 0) && al16(a.out1) && (a.out2 == nullptr || al16(a.out2));
+  const bool tmode = (mode == MODE_T3S2 || mode == MODE_T2S2);
+  a.xcd = opt.conv_xcd;
+  const int grid_y = tmode ? 4 : 1;
+  const bool fast = conv_mma_fast_eligible(dtype, a, nt);
+  bool wide = false;
+  // stride-2 3x3 forward, bf16, 128-multiples of output channels: 512-thread workgroups on 16-row tiles (two statistics tiles each)
+  // (measured per level, tools/s2_levels.py: 14-20 % faster from 128 input channels on; at 64 the two-chunk K loop leaves
+  // the lone workgroup's prologue / epilogue exposed: 0.63 vs 0.62 ms, so the two-workgroups-per-CU shape keeps that launch)
+  if (opt.conv_s2_wide && fast && mode == MODE_G3S2 && dtype == MIA_BF16 && nout % 128 == 0 && o1 % 128 == 0 && hout > 8 &&
+      (c1 + c2 >= 128 || opt.conv_s2_wide >= 2)) {
+    mt = 4;
+    a.tiles_y = ceil_div(hout, 16);
+    a.nblk_n = nout / 128;
+    wide = true;
+  }
+  int fam;
+  // conv64_dma: 1 = the one-pass two-destination input gradient only (measured faster there), 2 = every 64 -> 64 launch
+  if (a.acc_out) fam = fast ? MIA_CONV_FAM_ACC : MIA_EUNSUPPORTED;
+#ifdef MIA_EXPERIMENTS
+  else if (a.cr_y != nullptr) fam = (mt == 4 && conv64_eligible(mode, dtype, a)) ? MIA_CONV_FAM_CONV64 : MIA_EUNSUPPORTED;
+#endif
+  else if (a.nl_scale != nullptr) fam = (mt == 4 && conv64_eligible(mode, dtype, a)) ? MIA_CONV_FAM_NL : MIA_EUNSUPPORTED;
+  else if (opt.conv64 && opt.conv64_dma && (opt.conv64_dma >= 2 || a.o2 != 0) && mt == 4 && conv64_dma_eligible(mode, dtype, a)) fam = MIA_CONV_FAM_CONV64_DMA;
+  else if (opt.conv64 && mt == 4 && conv64_eligible(mode, dtype, a)) fam = MIA_CONV_FAM_CONV64;
+  else if (opt.conv_bt && mt == 4 && conv_bt_eligible(mode, dtype, a)) fam = MIA_CONV_FAM_CONV_BT;
+  // (strided 3x3 forward as a tap-gathered GEMM: measured 0.62 -> 0.51, 0.44 -> 0.40, 0.37 -> 0.35 ms at 64 / 128 / 256 input channels,
+  // 0.30 -> 0.30 at 512 in isolation (tools/s2_levels.py); step-time A/Bs could not resolve it (+-0.1 ms box noise), the per-kernel sums of
+  // two interleaved rocprofv3 pairs inside the cfg3 step can: 36.90 / 36.91 -> 36.77 / 36.77 ms of kernels, so it is on;
+  // conv_pw_s2 = 1 stops at 256 input channels, = 2 always)
+  else if (opt.conv_pw && (mode != MODE_G3S2 || opt.conv_pw_s2 >= 2 || (opt.conv_pw_s2 == 1 && c1 <= 256)) && conv_pw_eligible(mode, dtype, a))
+    fam = MIA_CONV_FAM_CONV_PW;
+  else if (fast) fam = wide ? MIA_CONV_FAM_S2_WIDE : MIA_CONV_FAM_FAST;
+  else fam = MIA_CONV_FAM_GENERIC;
+  return ConvPlan{fam, mt, nt, grid_y};
+}
+
+// The family mia_conv_mma / _nl / _acc would launch for a shape under the options as they are now: see include/mia_hip.h.
+extern "C" int mia_conv_mma_family(int mode, int dtype, int c1, int c2, int o1, int o2, int npad, int kpad, int hout, int wout,
+                                   int variant, int split) {
+  MIA_CHECK_ARG(mode >= 0 && mode <= MODE_G1, "mia_conv_mma_family: bad mode %d", mode);
+  MIA_CHECK_ARG(dtype == MIA_F32 || dtype == MIA_BF16, "mia_conv_mma_family: bad dtype %d", dtype);
+  MIA_CHECK_ARG(c1 > 0 && o1 > 0 && c2 >= 0 && o2 >= 0 && hout > 0 && wout > 0, "mia_conv_mma_family: bad shape");
+  const int kind = variant & 3;
+  MIA_CHECK_ARG(variant >= 0 && variant < 16 && kind != 3, "mia_conv_mma_family: bad variant %d", variant);
+  const int kb = dtype == MIA_BF16 ? 32 : 16;
+  MIA_CHECK_ARG(npad % 64 == 0 && npad >= o1 + o2 && kpad % kb == 0 && kpad >= c1 + c2, "mia_conv_mma_family: bad padding %d / %d", npad, kpad);
+  const MiaOptions opt = mia_options();
+  static const float dummy[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};  // stands for every operand: aligned, never read
+  ConvArgs a;
+  a.in1 = dummy; a.in2 = c2 ? dummy : nullptr; a.c1 = c1; a.c2 = c2; a.wp = dummy;
+  a.bias = (variant & MIA_CONV_VAR_BIAS) ? dummy : nullptr;
+  a.out1 = const_cast<float*>(dummy); a.out2 = o2 ? const_cast<float*>(dummy) : nullptr; a.o1 = o1; a.o2 = o2;
+  a.stats = (variant & MIA_CONV_VAR_STATS) ? const_cast<float*>(dummy) : nullptr;
+  a.N = 1; a.Hout = hout; a.Wout = wout;
+  switch (mode) {
+    case MODE_G3S2: case MODE_G2S2: a.Hin = 2 * hout; a.Win = 2 * wout; break;
+    case MODE_T3S2: a.Hin = (hout + 1) / 2; a.Win = (wout + 1) / 2; break;
+    case MODE_T2S2: a.Hin = hout / 2; a.Win = wout / 2; break;
+    default: a.Hin = hout; a.Win = wout; break;
+  }
+  a.npad = npad; a.kpad = kpad; a.flip = 0;
+  if (kind == 1) { a.nl_scale = dummy; a.nl_shift = dummy; a.nl_slope = 0.f; }
+  a.acc_out = kind == 2;
+  a.split = (dtype == MIA_F32 && opt.f32_split && split) ? opt.f32_split : 0;
+  return conv_select(opt, mode, dtype, a).family;
+}
+
 static int conv_mma_run(int mode, int dtype, const void* in1, int c1, const void* in2, int c2, const void* wpack,
                         int npad, int kpad, int flip_taps, const float* bias, void* out1, int o1, void* out2,
                         int o2, float* stat_partials, int n, int hin, int win, int hout, int wout, void* stream,
@@ -316,6 +399,8 @@ static int conv_mma_run(int mode, int dtype, const void* in1, int c1, const void
                         const void* wpack_split = nullptr) {
   MIA_CHECK_ARG(mode >= 0 && mode <= MODE_G1, "mia_conv_mma: bad mode %d", mode);
   MIA_CHECK_ARG(dtype == MIA_F32 || dtype == MIA_BF16, "mia_conv_mma: bad dtype %d", dtype);
+  // (the four parity classes of a transposed launch would each write the same per-tile entry: the last one to finish would win)
+  MIA_CHECK_ARG(stat_partials == nullptr || (mode != MODE_T3S2 && mode != MODE_T2S2), "mia_conv_mma: no statistics epilogue in the transposed mode %d", mode);
   MIA_CHECK_ARG(in1 && wpack && out1 && c1 > 0 && o1 > 0 && c2 >= 0 && o2 >= 0, "mia_conv_mma: null/empty operand");
   MIA_CHECK_ARG((c2 == 0) == (in2 == nullptr) && (o2 == 0) == (out2 == nullptr), "mia_conv_mma: split operand mismatch");
   MIA_CHECK_ARG(n > 0 && hin > 0 && win > 0 && hout > 0 && wout > 0, "mia_conv_mma: bad shape");
@@ -348,68 +433,36 @@ static int conv_mma_run(int mode, int dtype, const void* in1, int c1, const void
   if (cr_y != nullptr) {
     a.cr_y = cr_y; a.cr_scale = cr_coef[0]; a.cr_shift = cr_coef[1]; a.cr_xa = cr_coef[2]; a.cr_xb = cr_coef[3]; a.cr_slope = cr_slope;
   }
-  int th;
-  conv_tiles(opt, mode, hout, wout, &a.tiles_y, &a.tiles_x, &th);  // same snapshot as the launch below
-  int mt = th / 4;
-  const int nout = o1 + o2;
-  const int nt = nout > 32 ? 4 : (nout > 16 ? 2 : 1);
-  a.nblk_n = ceil_div(nout, 16 * nt);
-  a.st_tiles_y = a.tiles_y;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  a.vec_in = (c1 % epu == 0) && (c2 % epu == 0) && al16(in1) && (in2 == nullptr || al16(in2));
-  a.vec_out = (o1 % epu == 0) && (o2 % epu == 0) && al16(out1) && (out2 == nullptr || al16(out2));
-  const bool tmode = (mode == MODE_T3S2 || mode == MODE_T2S2);
-  a.xcd = opt.conv_xcd;
-  const int grid_y = tmode ? 4 : 1;
+  const ConvPlan p = conv_select(opt, mode, dtype, a);  // same snapshot as the launch below
   hipStream_t st = static_cast<hipStream_t>(stream);
   int rc;
-  const bool fast = conv_mma_fast_eligible(dtype, a, nt);
-  // stride-2 3x3 forward, bf16, 128-multiples of output channels: 512-thread workgroups on 16-row tiles (two statistics tiles each)
-  // (measured per level, tools/s2_levels.py: 14-20 % faster from 128 input channels on; at 64 the two-chunk K loop leaves
-  // the lone workgroup's prologue / epilogue exposed: 0.63 vs 0.62 ms, so the two-workgroups-per-CU shape keeps that launch)
-  if (opt.conv_s2_wide && fast && mode == MODE_G3S2 && dtype == MIA_BF16 && nout % 128 == 0 && o1 % 128 == 0 && hout > 8 &&
-      (c1 + c2 >= 128 || opt.conv_s2_wide >= 2)) {
-    mt = 4;
-    a.tiles_y = ceil_div(hout, 16);
-    a.nblk_n = nout / 128;
+  switch (p.family) {
+    case MIA_CONV_FAM_ACC:  // out += result: the tile kernel's epilogue reads the previous values
+      if (a.split && wpack_split != nullptr) { a.wp = wpack_split; a.wsplit = 1; }
+      rc = conv_mma_fast_launch(mode, dtype, a, p.mt, p.nt, p.grid_y, st);
+      break;
+    case MIA_CONV_FAM_NL:  // normalise-on-load: the register-staged 64-channel kernel is the one consumer that transforms
+    case MIA_CONV_FAM_CONV64:  // (and the column-reduce epilogue of probe builds: its epilogue overlaps the co-resident workgroup)
+      rc = conv64_launch(a, 0, opt.reserve_cus, st);
+      break;
+    case MIA_CONV_FAM_CONV64_DMA: rc = conv64_dma_launch(a, opt.reserve_cus, st); break;
+    case MIA_CONV_FAM_CONV_BT: rc = conv_bt_launch(a, opt.conv_bt_order, opt.reserve_cus, st); break;
+    case MIA_CONV_FAM_CONV_PW: rc = conv_pw_launch(mode, a, opt.reserve_cus, st); break;
+    case MIA_CONV_FAM_S2_WIDE:
+    case MIA_CONV_FAM_FAST:
+      if (a.split && wpack_split != nullptr) { a.wp = wpack_split; a.wsplit = 1; }
+      if (dtype == MIA_F32) { a.amax_out1 = static_cast<unsigned*>(amax_out1); a.amax_out2 = static_cast<unsigned*>(amax_out2); amax_out1 = amax_out2 = nullptr; }
+      rc = conv_mma_fast_launch(mode, dtype, a, p.mt, p.nt, p.grid_y, st);
+      break;
+    case MIA_CONV_FAM_GENERIC:
+      rc = dtype == MIA_BF16 ? dispatch<bf16_t>(mode, a, p.mt, p.nt, p.grid_y, st) : dispatch<float>(mode, a, p.mt, p.nt, p.grid_y, st);
+      break;
+    default:  // a variant asked for a shape outside its kernel's contract
+      if (acc_out) mia_set_error("mia_conv_mma_acc: shape outside the accumulating kernel's contract");
+      else if (cr_y != nullptr) mia_set_error("mia_conv_mma_cr: shape outside the column-reduce kernel's contract (ask mia_conv_cr_supported first)");
+      else mia_set_error("mia_conv_mma_nl: shape outside the normalise-on-load kernel's contract (ask mia_conv_nl_supported first)");
+      return p.family;
   }
-  // conv64_dma: 1 = the one-pass two-destination input gradient only (measured faster there), 2 = every 64 -> 64 launch
-  if (acc_out) {  // out += result: the tile kernel's epilogue reads the previous values
-    if (!fast) { mia_set_error("mia_conv_mma_acc: shape outside the accumulating kernel's contract"); return MIA_EUNSUPPORTED; }
-    if (a.split && wpack_split != nullptr) { a.wp = wpack_split; a.wsplit = 1; }
-    rc = conv_mma_fast_launch(mode, dtype, a, mt, nt, grid_y, st);
-  }
-#ifdef MIA_EXPERIMENTS
-  else if (cr_y != nullptr) {  // column-reduce epilogue: the 64-channel register kernel (its epilogue overlaps the co-resident workgroup)
-    if (!(mt == 4 && conv64_eligible(mode, dtype, a))) {
-      mia_set_error("mia_conv_mma_cr: shape outside the column-reduce kernel's contract (ask mia_conv_cr_supported first)");
-      return MIA_EUNSUPPORTED;
-    }
-    rc = conv64_launch(a, 0, opt.reserve_cus, st);
-  }
-#endif
-  else if (nl_scale != nullptr) {  // normalise-on-load: the register-staged 64-channel kernel is the one consumer that transforms
-    if (!(mt == 4 && conv64_eligible(mode, dtype, a))) {
-      mia_set_error("mia_conv_mma_nl: shape outside the normalise-on-load kernel's contract (ask mia_conv_nl_supported first)");
-      return MIA_EUNSUPPORTED;
-    }
-    rc = conv64_launch(a, 0, opt.reserve_cus, st);
-  }
-  else if (opt.conv64 && opt.conv64_dma && (opt.conv64_dma >= 2 || a.o2 != 0) && mt == 4 && conv64_dma_eligible(mode, dtype, a)) rc = conv64_dma_launch(a, opt.reserve_cus, st);
-  else if (opt.conv64 && mt == 4 && conv64_eligible(mode, dtype, a)) rc = conv64_launch(a, 0, opt.reserve_cus, st);
-  else if (opt.conv_bt && mt == 4 && conv_bt_eligible(mode, dtype, a)) rc = conv_bt_launch(a, opt.conv_bt_order, opt.reserve_cus, st);
-  // (strided 3x3 forward as a tap-gathered GEMM: measured 0.62 -> 0.51, 0.44 -> 0.40, 0.37 -> 0.35 ms at 64 / 128 / 256 input channels,
-  // 0.30 -> 0.30 at 512 in isolation (tools/s2_levels.py); step-time A/Bs could not resolve it (+-0.1 ms box noise), the per-kernel sums of
-  // two interleaved rocprofv3 pairs inside the cfg3 step can: 36.90 / 36.91 -> 36.77 / 36.77 ms of kernels, so it is on;
-  // conv_pw_s2 = 1 stops at 256 input channels, = 2 always)
-  else if (opt.conv_pw && (mode != MODE_G3S2 || opt.conv_pw_s2 >= 2 || (opt.conv_pw_s2 == 1 && c1 <= 256)) && conv_pw_eligible(mode, dtype, a))
-    rc = conv_pw_launch(mode, a, opt.reserve_cus, st);
-  else if (fast) {
-    if (a.split && wpack_split != nullptr) { a.wp = wpack_split; a.wsplit = 1; }
-    if (dtype == MIA_F32) { a.amax_out1 = static_cast<unsigned*>(amax_out1); a.amax_out2 = static_cast<unsigned*>(amax_out2); amax_out1 = amax_out2 = nullptr; }
-    rc = conv_mma_fast_launch(mode, dtype, a, mt, nt, grid_y, st);
-  }
-  else rc = dtype == MIA_BF16 ? dispatch<bf16_t>(mode, a, mt, nt, grid_y, st) : dispatch<float>(mode, a, mt, nt, grid_y, st);
   if (rc != MIA_OK) return rc;
   MIA_LAUNCH_CHECK();
   // output maxima the launched kernel did not fold in its epilogue (generic shapes): a separate pass each

@@ -196,6 +196,37 @@ extern "C" int mia_wgrad_geometry(int mode, int dtype, int hy, int wy, int* tile
   return MIA_OK;
 }
 
+// Which kernel family serves a weight gradient: ONE pure function of the options snapshot and the launch description, shared by the
+// launch path (conv_wgrad_run switches on its result) and by the query mia_wgrad_family.  chan_ok: every channel count a whole number
+// of 16-byte units on aligned tensors; fast: the bf16 branch-free contract (chan_ok and 32-bit byte offsets); fits32: the same
+// offset bound for fp32 tensors; nl: normalise-on-load variant (MIA_EUNSUPPORTED outside its kernel's contract).
+static int wgrad_select(const MiaOptions& o, int mode, int dtype, int c1, int c2, int cdy, int npad, bool chan_ok, bool fast,
+                        bool fits32, bool nl) {
+  if (nl) return (fast && mode == MODE_W3S1 && c2 == 0) ? MIA_WGRAD_FAM_2WG_NL : MIA_EUNSUPPORTED;
+  const int th = wgrad_tile_h(o, mode, dtype, fast);
+  const bool bt = fast && th == 4 && cdy % 128 == 0 && npad % 128 == 0 &&  // 512-thread workgroups on 128 n x 64 k blocks
+                  (mode == MODE_W2S2 ? o.wgrad_bt >= 1 && o.wgrad_t2 : o.wgrad_bt);
+  if (fast && wgrad_w96(o, mode, dtype, c1, c2, cdy)) return MIA_WGRAD_FAM_DMA96;
+  if (bt) return MIA_WGRAD_FAM_BT;
+  if (fast && th == 4 && mode == MODE_W3S1) return MIA_WGRAD_FAM_DMA;
+  if (fast && wgrad_two_wg(mode, dtype)) return MIA_WGRAD_FAM_2WG;  // stride-2 / transposed shapes stay on the one-workgroup-per-CU kernel
+  if (fast) return MIA_WGRAD_FAM_TILE_FAST;
+  if (dtype == MIA_F32 && chan_ok && fits32) return (cdy <= 32 && c1 <= 32 && c2 <= 32) ? MIA_WGRAD_FAM_F32_NARROW : MIA_WGRAD_FAM_F32_FAST;
+  return MIA_WGRAD_FAM_GENERIC;
+}
+
+// The family mia_conv_wgrad / _nl would launch for a shape under the options as they are now: see include/mia_hip.h.
+extern "C" int mia_wgrad_family(int mode, int dtype, int c1, int c2, int cdy, int npad, int variant, int split) {
+  MIA_CHECK_ARG(mode >= 0 && mode <= MODE_W2S2, "mia_wgrad_family: bad mode %d", mode);
+  MIA_CHECK_ARG(dtype == MIA_F32 || dtype == MIA_BF16, "mia_wgrad_family: bad dtype");
+  MIA_CHECK_ARG(c1 > 0 && c2 >= 0 && cdy > 0 && npad % 64 == 0 && npad >= cdy, "mia_wgrad_family: bad shape");
+  MIA_CHECK_ARG(variant == 0 || variant == 1, "mia_wgrad_family: bad variant %d", variant);
+  (void)split;  // the split-f16 product form is a template argument of the fp32 families' kernel, not a family of its own
+  const int epu = dtype == MIA_BF16 ? 8 : 4;
+  const bool chan_ok = c1 % epu == 0 && c2 % epu == 0 && cdy % epu == 0;
+  return wgrad_select(mia_options(), mode, dtype, c1, c2, cdy, npad, chan_ok, dtype == MIA_BF16 && chan_ok, true, variant == 1);
+}
+
 static int conv_wgrad_run(int mode, int dtype, const void* x1, int c1, const void* x2, int c2, const void* dy,
                           int cdy, float* slabs, int ksplit, int npad, int kpad, int n, int hx, int wx, int hy,
                           int wy, void* stream, const float* nl_scale, const float* nl_shift, float nl_slope,
@@ -235,42 +266,36 @@ static int conv_wgrad_run(int mode, int dtype, const void* x1, int c1, const voi
     a.opt |= 16;
     fgrid = dim3(fgrid.x * (unsigned)(ceil_div(ksplit, 8) * 8), 1);
   }
-  if (nl_scale != nullptr) {  // normalise-on-load: the register-staged two-workgroup kernel is the one that transforms
-    if (!(fast && mode == MODE_W3S1 && c2 == 0)) {
-      mia_set_error("mia_conv_wgrad_nl: shape outside the normalise-on-load kernel's contract (ask mia_wgrad_nl_supported first)");
-      return MIA_EUNSUPPORTED;
-    }
-    a.tiles_y = ceil_div(hy, 8);
-    a.tiles_x = ceil_div(wy, 16);
-    wgrad_ring_launch(WG_RING_2WG_NL, a, fgrid, st);
-    MIA_LAUNCH_CHECK();
-    return MIA_OK;
-  }
+  const bool fits32 = (size_t)hx * wx * (c1 > c2 ? c1 : c2) * 4 < lim && (size_t)hy * wy * cdy * 4 < lim;
+  const int fam = wgrad_select(o, mode, dtype, c1, c2, cdy, npad, chan_ok, fast, fits32, nl_scale != nullptr);
   const int th = wgrad_tile_h(o, mode, dtype, fast);
   a.tiles_y = ceil_div(hy, th);
   a.tiles_x = ceil_div(wy, 16);
-  const bool bt = fast && th == 4 && cdy % 128 == 0 && npad % 128 == 0 &&  // 512-thread workgroups on 128 n x 64 k blocks
-                  (mode == MODE_W2S2 ? o.wgrad_bt >= 1 && o.wgrad_t2 : o.wgrad_bt);
-  if (fast && wgrad_w96(o, mode, dtype, c1, c2, cdy)) {  // 96-wide ring blocks: one block per pixel tile where 64-wide ones need 2 x 2
-    const unsigned ncol = (unsigned)(ceil_div(cdy, 96) * (ceil_div(c1, 96) + ceil_div(c2, 96)));
-    const dim3 wgrid = (a.opt & 16) ? dim3(ncol * (unsigned)(ceil_div(ksplit, 8) * 8), 1) : dim3(ncol, ksplit);
-    a.tiles_y = ceil_div(hy, 4);
-    wgrad_ring_launch(WG_RING_DMA96, a, wgrid, st);
-  } else if (bt) {
-    wgrad_bt_launch(mode, a, dim3(fgrid.x / 2, fgrid.y), st);  // half as many column blocks
-  } else if (fast && th == 4 && mode == MODE_W3S1) {
-    wgrad_ring_launch(WG_RING_DMA, a, fgrid, st);
-  } else if (fast && wgrad_two_wg(mode, dtype)) {  // stride-2 / transposed shapes stay on the one-workgroup-per-CU kernel
-    wgrad_ring_launch(WG_RING_2WG, a, fgrid, st);
-  } else if (fast) {
-    wgrad_tile_launch(mode, dtype, true, false, false, a, fgrid, st);
-  } else if (dtype == MIA_F32 && chan_ok && (size_t)hx * wx * (c1 > c2 ? c1 : c2) * 4 < lim &&
-             (size_t)hy * wy * cdy * 4 < lim) {
-    const bool narrow = cdy <= 32 && c1 <= 32 && c2 <= 32;  // 32-channel layers: half-width blocks, all four waves busy
-    if (narrow && mode == MODE_W3S1) a.tiles_y = ceil_div(hy, 8);  // (8-row tiles: wgrad_f32_fast_kernel N8)
-    wgrad_tile_launch(mode, dtype, true, narrow, split, a, fgrid, st);
-  } else {
-    wgrad_tile_launch(mode, dtype, false, false, false, a, grid, st);
+  switch (fam) {
+    case MIA_WGRAD_FAM_2WG_NL:  // normalise-on-load: the register-staged two-workgroup kernel is the one that transforms
+      a.tiles_y = ceil_div(hy, 8);
+      wgrad_ring_launch(WG_RING_2WG_NL, a, fgrid, st);
+      break;
+    case MIA_WGRAD_FAM_DMA96: {  // 96-wide ring blocks: one block per pixel tile where 64-wide ones need 2 x 2
+      const unsigned ncol = (unsigned)(ceil_div(cdy, 96) * (ceil_div(c1, 96) + ceil_div(c2, 96)));
+      const dim3 wgrid = (a.opt & 16) ? dim3(ncol * (unsigned)(ceil_div(ksplit, 8) * 8), 1) : dim3(ncol, ksplit);
+      a.tiles_y = ceil_div(hy, 4);
+      wgrad_ring_launch(WG_RING_DMA96, a, wgrid, st);
+      break;
+    }
+    case MIA_WGRAD_FAM_BT: wgrad_bt_launch(mode, a, dim3(fgrid.x / 2, fgrid.y), st); break;  // half as many column blocks
+    case MIA_WGRAD_FAM_DMA: wgrad_ring_launch(WG_RING_DMA, a, fgrid, st); break;
+    case MIA_WGRAD_FAM_2WG: wgrad_ring_launch(WG_RING_2WG, a, fgrid, st); break;
+    case MIA_WGRAD_FAM_TILE_FAST: wgrad_tile_launch(mode, dtype, true, false, false, a, fgrid, st); break;
+    case MIA_WGRAD_FAM_F32_NARROW:  // 32-channel layers: half-width blocks, all four waves busy
+      if (mode == MODE_W3S1) a.tiles_y = ceil_div(hy, 8);  // (8-row tiles: wgrad_f32_fast_kernel N8)
+      wgrad_tile_launch(mode, dtype, true, true, split, a, fgrid, st);
+      break;
+    case MIA_WGRAD_FAM_F32_FAST: wgrad_tile_launch(mode, dtype, true, false, split, a, fgrid, st); break;
+    case MIA_WGRAD_FAM_GENERIC: wgrad_tile_launch(mode, dtype, false, false, false, a, grid, st); break;
+    default:
+      mia_set_error("mia_conv_wgrad_nl: shape outside the normalise-on-load kernel's contract (ask mia_wgrad_nl_supported first)");
+      return fam;
   }
   MIA_LAUNCH_CHECK();
   return MIA_OK;

@@ -10,6 +10,9 @@
 #include <type_traits>
 
 enum { MODE_W3S1 = 0, MODE_W3S2 = 1, MODE_W2S2 = 2 };
+// kernel families of the dispatcher (conv_wgrad.hip wgrad_select; the values of include/mia_hip.h MIA_WGRAD_FAM_*)
+enum { MIA_WGRAD_FAM_DMA96 = 0, MIA_WGRAD_FAM_BT = 1, MIA_WGRAD_FAM_DMA = 2, MIA_WGRAD_FAM_2WG = 3, MIA_WGRAD_FAM_2WG_NL = 4,
+       MIA_WGRAD_FAM_TILE_FAST = 5, MIA_WGRAD_FAM_F32_FAST = 6, MIA_WGRAD_FAM_F32_NARROW = 7, MIA_WGRAD_FAM_GENERIC = 8 };
 
 struct WgArgs {
   const void* x1; const void* x2; int c1; int c2;

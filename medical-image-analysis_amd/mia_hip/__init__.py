@@ -19,6 +19,10 @@ LIB_PATH = os.environ.get("MIA_HIP_LIB") or os.path.join(HERE, "libmia_hip.so") 
 F32, BF16 = 0, 1
 CONV_G3S1, CONV_G3S2, CONV_G2S2, CONV_T3S2, CONV_T2S2, CONV_G1 = range(6)
 WGRAD_3S1, WGRAD_3S2, WGRAD_2S2 = range(3)
+# kernel families reported by mia_conv_mma_family / mia_wgrad_family (include/mia_hip.h MIA_CONV_FAM_* / MIA_WGRAD_FAM_*)
+CONV_FAM = {name: i for i, name in enumerate(("GENERIC", "FAST", "S2_WIDE", "CONV64", "CONV64_DMA", "CONV_BT", "CONV_PW", "NL", "ACC"))}
+CONV_VAR_PLAIN, CONV_VAR_NL, CONV_VAR_ACC, CONV_VAR_STATS, CONV_VAR_BIAS = 0, 1, 2, 4, 8
+WGRAD_FAM = {name: i for i, name in enumerate(("DMA96", "BT", "DMA", "2WG", "2WG_NL", "TILE_FAST", "F32_FAST", "F32_NARROW", "GENERIC"))}
 NORM_INSTANCE, NORM_BATCH = 0, 1
 LOSS_SOFTMAX, LOSS_DO_BG, LOSS_BATCH, LOSS_SQUARED, LOSS_DENSE = 1, 2, 4, 8, 16
 SEGLOSS_SOFTMAX, SEGLOSS_DO_BG, SEGLOSS_BATCH, SEGLOSS_LABEL_U8, SEGLOSS_IGNORE = 1, 2, 4, 8, 16
