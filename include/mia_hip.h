@@ -217,6 +217,12 @@ int mia_stem_wgrad(const void* x, int x_dtype, const void* dy, int dtype, float*
 int mia_stem_wgrad_fused(const void* x, int x_dtype, const void* dz, const void* y, int dtype, const float* scale,
                          const float* shift, const float* xa, const float* xb, const float* c1, const float* c2, float slope,
                          float* workspace, float* grad, int n, int h, int wd, int c0, int accumulate, void* stream);
+/* Input gradient of the stem (csrc/stem_dgrad.hip): dx[n][y][x] = sum_co sum_(a,b) w[co][3a+b] * dy[n][y+1-a][x+1-b][co], dy outside
+ * the image = 0; dy NHWC in `dtype` (16-byte aligned), w the [C0][9] fp32 parameter, dx the fp32 [N][H][W] image gradient; fp32
+ * accumulation on the matrix cores (bf16: w enters as two bf16 parts, hi + lo).  Eligibility is mia_stem_fwd's: c0 % 8 == 0 (bf16) /
+ * c0 % 4 == 0 (fp32), c0 <= 256, any h, wd >= 1.  One stream over dy, no float atomics: bit-identical from run to run.  Every check
+ * happens before any launch.  Not fused with the norm backward: the caller materialises dy (mia_norm_act_bwd) first. */
+int mia_stem_dgrad(const void* dy, int dtype, const float* w, float* dx, int n, int h, int wd, int c0, void* stream);
 
 #define MIA_WGRAD_3S1 0
 #define MIA_WGRAD_3S2 1
@@ -320,7 +326,8 @@ int mia_norm_act_bwd_apply_sync(const void* dz, const void* dz2, const void* y, 
                                 int accumulate, void* amax_out, void* stream);
 
 /* ------------------------------------------------------------------ 1x1 head + Dice/CE loss */
-/* seg_output = Conv2d(c0, K1, 1) (unet.py:176), K1 <= 8.  Logits are fp32 with element strides (osn, osk, osp). */
+/* seg_output = Conv2d(c0, K1, 1) (unet.py:176), K1 <= 8.  Logits are fp32 with element strides (osn, osk, osp).  mia_head_bwd: dx may
+ * be NULL (no input gradient); dw == db == NULL with dx given computes the input gradient alone (workspace is then unused). */
 int mia_head_fwd(const void* x, int dtype, const float* w, const float* b, float* logits, int n, int64_t hw, int c0, int k1,
                  int64_t osn, int64_t osk, int64_t osp, void* stream);
 int mia_head_bwd_workspace(int c0, int k1); /* floats */
@@ -694,6 +701,35 @@ int mia_cps_fwd(const float* za, const float* zb, const float* dyn_dev, int nb, 
 int mia_cps_bwd(const float* za, const float* zb, const unsigned char* code, const float* dyn_dev, const float* grad_out, float* dza,
                 float* dzb, int nb, int64_t hw, int k1, int64_t asn, int64_t ask, int64_t asp, int64_t bsn, int64_t bsk, int64_t bsp,
                 int64_t gasn, int64_t gask, int64_t gasp, int64_t gbsn, int64_t gbsk, int64_t gbsp, void* stream);
+
+/* ------------------------------------------------------------------ virtual adversarial training (csrc/vat.hip) */
+/* KL distance between two fp32 logits tensors [nb][k1][hw], each addressed by its own (sn, sk, sp) / (tsn, tsk, tsp) element strides
+ * like mia_consistency_fwd (planar, channels-last and scalar layout classes, batch slices):
+ *   p = softmax(zt) (the target: no gradient), log q = z - logsumexp(z), log p likewise
+ *   L = coef * sum_pix sum_k p_k (log p_k - log q_k),  coef = 1 / den;  a term with p_k == 0 contributes 0
+ * den is the caller's: nb * hw for the per-pixel mean, nb for "batchmean".  dyn_dev = {weight, ...} (device, read when the kernels
+ * run; NULL = weight 1).  out = {weight * L, L, weight}; coef[0] = 1 / den for the backward.  Both soft-maxes and every partial sum
+ * are in double; one finalize block adds the block partials in a fixed order; no float atomics.
+ * Backward: dz_j = grad_out * weight * coef * (q_j - p_j), written by (gsn, gsk, gsp); grad_out: device fp32 (NULL = 1).
+ * slabs = blocks per image of the forward; workspace: mia_kl_workspace 4-byte words.  Limits: 1 <= k1 <= 8, nb * hw < 2^31.  Every
+ * check happens before any launch. */
+int mia_kl_workspace(int nb, int slabs); /* 4-byte words; < 0 for a bad shape */
+int mia_kl_fwd(const float* z, const float* zt, const float* dyn_dev, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
+               int64_t tsn, int64_t tsk, int64_t tsp, double den, int slabs, float* workspace, float* coef, float* out, void* stream);
+int mia_kl_bwd(const float* z, const float* zt, const float* coef, const float* dyn_dev, const float* grad_out, float* dz, int nb,
+               int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t tsn, int64_t tsk, int64_t tsp, int64_t gsn, int64_t gsk,
+               int64_t gsp, void* stream);
+/* u[nb * per] ~ U[-0.5, 0.5) (24 bits, every value exact) from Philox4x32-10, the generator of mia_dropout_mask: element i is word
+ * i & 3 of counter (i >> 2, offset) under key `seed`, so it depends on (seed, offset, i) only -- a sample's values do not depend on nb. */
+int mia_vat_noise(float* u, int nb, int64_t per, uint64_t seed, uint64_t offset, void* stream);
+/* out[n] = sum of x[n][0 .. per)^2 in double, rounded once.  workspace: mia_sample_sumsq_workspace 4-byte words. */
+int mia_sample_sumsq_workspace(int nb, int64_t per); /* 4-byte words; < 0 for a bad shape */
+int mia_sample_sumsq(const float* x, int nb, int64_t per, float* workspace, float* out, void* stream);
+/* out = x + s * (gscale * g) / (gscale * sqrt(sumsq[n]) + 1e-8) over [nb][per] fp32 buffers, in double, rounded once; s = *scale_dev
+ * (device) when given, else `scale`.  With gscale = xi this is the published `_l2_normalize(d.grad)` times s when g is the gradient
+ * with respect to x + xi d rather than d.  g == 0 gives out = x.  16-byte accesses when x, g and out are 16-byte aligned. */
+int mia_vat_perturb(const float* x, const float* g, const float* sumsq, float gscale, float scale, const float* scale_dev, float* out,
+                    int nb, int64_t per, void* stream);
 
 /* ------------------------------------------------------------------ prediction (entry/fugc2025/predict.py) */
 /* Ensemble reduction of predict.py:144-161 (`P = P + seg.softmax(1)` per fold model) and the arg-max of :55-57, one pass per

@@ -605,7 +605,9 @@ extern "C" int mia_head_bwd_workspace(int c0, int k1) { return HEAD_BWD_BLOCKS *
 extern "C" int mia_head_bwd(const float* dlogits, const void* x, int dtype, const float* w, void* dx, float* dw, float* db,
                             float* workspace, int n, int64_t hw, int c0, int k1, int64_t gsn, int64_t gsk, int64_t gsp,
                             int accumulate, void* stream) {
-  MIA_CHECK_ARG(dlogits && x && w && dw && db && workspace && n > 0 && hw > 0 && c0 > 0, "mia_head_bwd: bad arguments");
+  // dw == db == NULL: the input gradient alone (a backward with frozen parameters); the weight kernels and the workspace are not touched
+  const bool wg = dw != nullptr || db != nullptr;
+  MIA_CHECK_ARG(dlogits && x && w && (wg ? (dw && db && workspace) : dx != nullptr) && n > 0 && hw > 0 && c0 > 0, "mia_head_bwd: bad arguments");
   MIA_CHECK_ARG(k1 >= 1 && k1 <= MAXK, "mia_head_bwd: k1=%d not in [1,%d]", k1, MAXK);
   const int64_t npix = (int64_t)n * hw;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -621,29 +623,29 @@ extern "C" int mia_head_bwd(const float* dlogits, const void* x, int dtype, cons
     const int iblocks = (int)((npix + lanes - 1) / lanes < 16384 ? (npix + lanes - 1) / lanes : 16384);
     if (dtype == MIA_BF16) {
       if (dx) HEAD_DISPATCH(head_bwd_input_fast_kernel, bf16_t, dim3(iblocks), dlogits, w, static_cast<bf16_t*>(dx), (int)npix, gsp, gsk);
-      HEAD_DISPATCH(head_bwd_weight_fast_kernel, bf16_t, dim3(wblocks), dlogits, static_cast<const bf16_t*>(x), workspace, (int)npix, gsp, gsk);
+      if (wg) { HEAD_DISPATCH(head_bwd_weight_fast_kernel, bf16_t, dim3(wblocks), dlogits, static_cast<const bf16_t*>(x), workspace, (int)npix, gsp, gsk); }
     } else {
       if (dx) HEAD_DISPATCH(head_bwd_input_fast_kernel, float, dim3(iblocks), dlogits, w, static_cast<float*>(dx), (int)npix, gsp, gsk);
-      HEAD_DISPATCH(head_bwd_weight_fast_kernel, float, dim3(wblocks), dlogits, static_cast<const float*>(x), workspace, (int)npix, gsp, gsk);
+      if (wg) { HEAD_DISPATCH(head_bwd_weight_fast_kernel, float, dim3(wblocks), dlogits, static_cast<const float*>(x), workspace, (int)npix, gsp, gsk); }
     }
   } else if (vec && (dtype == MIA_BF16 || dtype == MIA_F32)) {
     const int64_t units = npix * (c0 / epu);
     const int vblocks = (int)((units + 255) / 256 < 16384 ? (units + 255) / 256 : 16384);
     if (dtype == MIA_BF16) {
       if (dx) hipLaunchKernelGGL(head_bwd_input_vec_kernel<bf16_t>, dim3(vblocks), dim3(256), k1 * c0 * 4, st, dlogits, w, static_cast<bf16_t*>(dx), npix, c0, k1, gsp, gsk, gsn, hw);
-      hipLaunchKernelGGL(head_bwd_weight_vec_kernel<bf16_t>, dim3(wblocks), dim3(256), (256 / (c0 / epu)) * (c0 + 1) * 4, st, dlogits, static_cast<const bf16_t*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw);
+      if (wg) { hipLaunchKernelGGL(head_bwd_weight_vec_kernel<bf16_t>, dim3(wblocks), dim3(256), (256 / (c0 / epu)) * (c0 + 1) * 4, st, dlogits, static_cast<const bf16_t*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw); }
     } else {
       if (dx) hipLaunchKernelGGL(head_bwd_input_vec_kernel<float>, dim3(vblocks), dim3(256), k1 * c0 * 4, st, dlogits, w, static_cast<float*>(dx), npix, c0, k1, gsp, gsk, gsn, hw);
-      hipLaunchKernelGGL(head_bwd_weight_vec_kernel<float>, dim3(wblocks), dim3(256), (256 / (c0 / epu)) * (c0 + 1) * 4, st, dlogits, static_cast<const float*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw);
+      if (wg) { hipLaunchKernelGGL(head_bwd_weight_vec_kernel<float>, dim3(wblocks), dim3(256), (256 / (c0 / epu)) * (c0 + 1) * 4, st, dlogits, static_cast<const float*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw); }
     }
   } else if (dtype == MIA_BF16) {
     if (dx) hipLaunchKernelGGL(head_bwd_input_kernel<bf16_t>, dim3(blocks), dim3(256), k1 * c0 * 4, st, dlogits, w, static_cast<bf16_t*>(dx), npix, c0, k1, gsp, gsk, gsn, hw);
-    hipLaunchKernelGGL(head_bwd_weight_kernel<bf16_t>, dim3(wblocks), dim3(256), 512 * 4, st, dlogits, static_cast<const bf16_t*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw);
+    if (wg) { hipLaunchKernelGGL(head_bwd_weight_kernel<bf16_t>, dim3(wblocks), dim3(256), 512 * 4, st, dlogits, static_cast<const bf16_t*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw); }
   } else if (dtype == MIA_F32) {
     if (dx) hipLaunchKernelGGL(head_bwd_input_kernel<float>, dim3(blocks), dim3(256), k1 * c0 * 4, st, dlogits, w, static_cast<float*>(dx), npix, c0, k1, gsp, gsk, gsn, hw);
-    hipLaunchKernelGGL(head_bwd_weight_kernel<float>, dim3(wblocks), dim3(256), 512 * 4, st, dlogits, static_cast<const float*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw);
+    if (wg) { hipLaunchKernelGGL(head_bwd_weight_kernel<float>, dim3(wblocks), dim3(256), 512 * 4, st, dlogits, static_cast<const float*>(x), workspace, npix, c0, k1, gsp, gsk, gsn, hw); }
   } else { mia_set_error("mia_head_bwd: bad dtype"); return MIA_EARG; }
-  hipLaunchKernelGGL(head_bwd_final_kernel, dim3(ceil_div(k1 * (c0 + 1), 16)), dim3(256), 0, st, workspace, wblocks, k1, c0, dw, db, accumulate);
+  if (wg) { hipLaunchKernelGGL(head_bwd_final_kernel, dim3(ceil_div(k1 * (c0 + 1), 16)), dim3(256), 0, st, workspace, wblocks, k1, c0, dw, db, accumulate); }
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }

@@ -301,6 +301,8 @@ def to_nhwc(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
             return x.reshape(n, h, w, 1)  # NCHW with C=1 is already NHWC
         if sc == 1 and sw == c and (h == 1 or sh == w * c) and (n == 1 or sn == h * w * c):
             return x.permute(0, 2, 3, 1)  # channels_last storage: zero-copy
+    if x.requires_grad and torch.is_grad_enabled():
+        return _RelayoutFn.apply(x, dtype)  # the image itself wants a gradient (VAT, saliency): keep the graph through the kernel
     if h > 1 and sh != w * sw:
         x = x.contiguous()
         sn, sc, sh, sw = x.stride()
@@ -308,6 +310,30 @@ def to_nhwc(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     call("mia_relayout", _p(x), _dt(x), _p(out), _dt(out), n, c, _c_i64(h * w), _c_i64(sn), _c_i64(sc), _c_i64(sw),
          _c_i64(h * w * c), _c_i64(1), _c_i64(c), _stream())
     return out
+
+
+class _RelayoutFn(torch.autograd.Function):
+    """`to_nhwc` through `mia_relayout` for an input that requires a gradient; the backward is the same kernel in the opposite
+    direction, back to the image's layout (its strides where H and W collapse, contiguous NCHW otherwise) and dtype."""
+
+    @staticmethod
+    def forward(ctx, x, dtype):
+        ctx.save_for_backward(x)  # for its shape, strides and dtype
+        return to_nhwc(x.detach(), dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        n, c, h, w = x.shape
+        g = g.contiguous()
+        dx = torch.empty_like(x)  # x's strides where x is dense, contiguous otherwise
+        sn, sc, sh, sw = dx.stride()
+        if h > 1 and sh != w * sw:
+            dx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+            sn, sc, sh, sw = dx.stride()
+        call("mia_relayout", _p(g), _dt(g), _p(dx), _dt(dx), n, c, _c_i64(h * w), _c_i64(h * w * c), _c_i64(1), _c_i64(c),
+             _c_i64(sn), _c_i64(sc), _c_i64(sw), _stream())
+        return dx, None
 
 
 def nhwc_as_nchw(x: torch.Tensor) -> torch.Tensor:
@@ -683,6 +709,24 @@ class BatchSync:
         return t
 
 
+_BN_TRACKING = True
+
+
+class no_bn_tracking:
+    """Context manager: training-mode batch norm still normalises with the batch statistics, but the running statistics and
+    `num_batches_tracked` stay untouched (the kernels get no pointer to them).  For extra forward passes that are not training steps,
+    e.g. the power iteration of virtual adversarial training (the published code's `_disable_tracking_bn_stats`)."""
+
+    def __enter__(self):
+        global _BN_TRACKING
+        self._was, _BN_TRACKING = _BN_TRACKING, False
+
+    def __exit__(self, *exc):
+        global _BN_TRACKING
+        _BN_TRACKING = self._was
+        return False
+
+
 def _norm_finalize(ctx, cfg: NormCfg, stats, gamma, beta, y) -> torch.Tensor:
     """The [5, N, C] per-(n,c) coefficient table (xa, xb, scale, shift, sum_y) of a block with raw conv output y, from the conv-epilogue
     partials; batch statistics cover every rank when cfg.sync is set, and ctx.sync then keeps the group for backward."""
@@ -690,10 +734,12 @@ def _norm_finalize(ctx, cfg: NormCfg, stats, gamma, beta, y) -> torch.Tensor:
     hw = h * w
     coefs = torch.empty((5, n, cout), device=y.device, dtype=torch.float32)
     ctx.sync = sync = cfg.sync if (cfg.sync is not None and cfg.mode == NORM_BATCH and cfg.training and cfg.sync.world > 1) else None
+    track = _BN_TRACKING or not cfg.training  # (eval batch norm READS the running statistics)
+    rmean, rvar, nbatch = (cfg.running_mean, cfg.running_var, cfg.num_batches) if track else (None, None, None)
     if sync is None:
         call("mia_norm_finalize", _p(stats), n, 0 if stats is None else stats.shape[1], cout, _c_i64(hw), cfg.mode, int(cfg.training),
              _p(cfg.drop_scale), _p(gamma.detach()), _p(beta.detach()), _c_float(cfg.eps), _c_float(cfg.momentum),
-             _p(cfg.running_mean), _p(cfg.running_var), _p(cfg.num_batches), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]),
+             _p(rmean), _p(rvar), _p(nbatch), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]),
              _p(coefs[3]), _p(coefs[4]), _stream())
         return coefs
     local = torch.empty((3, cout), device=stats.device, dtype=torch.float32)
@@ -701,8 +747,8 @@ def _norm_finalize(ctx, cfg: NormCfg, stats, gamma, beta, y) -> torch.Tensor:
          _p(coefs[1]), _p(local), _stream())
     gathered = sync.all_gather(local)
     call("mia_norm_finalize_sync", _p(gathered), sync.world, n, cout, _c_i64(hw), _p(cfg.drop_scale), _p(gamma.detach()),
-         _p(beta.detach()), _c_float(cfg.eps), _c_float(cfg.momentum), _p(cfg.running_mean), _p(cfg.running_var),
-         _p(cfg.num_batches), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]), _p(coefs[3]), _p(coefs[4]), _stream())
+         _p(beta.detach()), _c_float(cfg.eps), _c_float(cfg.momentum), _p(rmean), _p(rvar),
+         _p(nbatch), _p(coefs[0]), _p(coefs[1]), _p(coefs[2]), _p(coefs[3]), _p(coefs[4]), _stream())
     return coefs
 
 
@@ -860,6 +906,17 @@ def _block_wgrad(nb: _NormBwd, x1, x2, weight, stride: int, nl, dy, stem: bool =
     return dw
 
 
+def _stem_dgrad(dy, weight, x1) -> torch.Tensor:
+    """Step 3 for the stem: the image gradient [N, H, W, 1] from dy (`mia_stem_dgrad`, fp32), in the image's dtype."""
+    n, h, w, cout = dy.shape
+    w2 = weight.detach().reshape(cout, 9)
+    if not w2.is_contiguous():
+        w2 = w2.contiguous()
+    dx = torch.empty((n, h, w, 1), device=dy.device, dtype=torch.float32)
+    call("mia_stem_dgrad", _p(dy), _dt(dy), _p(w2), _p(dx), n, h, w, cout, _stream())
+    return dx if x1.dtype == torch.float32 else cast_nhwc(dx, x1.dtype)
+
+
 def _block_dgrad(x1, x2, weight, dy, stride: int, nl, dup_in: bool, need1: bool, need2: bool):
     """Step 3 of a block's backward, where somebody needs it: (dx1, dx2) from dy.  nl = (coefs, slope): x1 is the previous block's raw output."""
     dx1 = dx2 = None
@@ -918,7 +975,8 @@ class PlainBlockFn(torch.autograd.Function):
         out_dtype = out_dtype or x1.dtype
         cout = weight.shape[0]
         assert not (lazy and dup)
-        stem = (weight.shape[1] == 1 and x2 is None and stride == 1 and x1.shape[3] == 1 and not x1.requires_grad
+        # (an image that requires a gradient keeps the stem: same logits bit for bit, and backward has `mia_stem_dgrad`)
+        stem = (weight.shape[1] == 1 and x2 is None and stride == 1 and x1.shape[3] == 1
                 and cout % (8 if out_dtype == torch.bfloat16 else 4) == 0 and cout <= 256 and nl_coefs is None)
         if stem:
             z = PlainBlockFn._stem_forward(ctx, x1, weight, bias, gamma, beta, cfg, out_dtype, slope, lazy)
@@ -986,13 +1044,21 @@ class PlainBlockFn(torch.autograd.Function):
         dz, dz2 = pieces[0], (pieces[1] if len(pieces) > 1 else None)
         if dz2 is not None and not (lib().mia_norm_two_piece_ok(_dt(y), y.shape[3]) and dz.data_ptr() % 16 == 0 and dz2.data_ptr() % 16 == 0):
             dz, dz2 = dz + dz2, None  # shapes outside the vectorised kernels: one explicit sum
-        nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope, (gamma, ctx.small[1], ctx.small[0]))
-        dy = nb.run(dz, dz2, ctx.sync, ctx.stem and ctx.sync is None and FUSE_STEM_BWD)
+        need_w = any(ctx.needs_input_grad[2:6])  # frozen parameters (ops.frozen_parameters): no weight gradient, no claimed slice
+        nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope, (gamma, ctx.small[1], ctx.small[0]) if need_w else None)
+        # the stem's dy is formed on load by its weight gradient -- unless the image wants a gradient too: `mia_stem_dgrad` reads dy
+        on_load = ctx.stem and ctx.sync is None and FUSE_STEM_BWD and need_w and not ctx.needs_input_grad[0]
+        dy = nb.run(dz, dz2, ctx.sync, on_load)
         nl = None if nl_coefs is None else (nl_coefs, ctx.nl_slope)
-        dw = _block_wgrad(nb, x1, x2, weight, ctx.stride, nl, dy, ctx.stem, dz, dz2)
+        dw = _block_wgrad(nb, x1, x2, weight, ctx.stride, nl, dy, ctx.stem, dz, dz2) if need_w else None
         dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):  # (never the stem: its input needs no gradient)
+        if ctx.stem:
+            if ctx.needs_input_grad[0]:
+                dx1 = _stem_dgrad(dy, weight, x1)
+        elif ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1]):
             dx1, dx2 = _block_dgrad(x1, x2, weight, dy, ctx.stride, nl, ctx.dup_in, *ctx.needs_input_grad[:2])
+        if not need_w:
+            return (dx1, dx2) + (None,) * 12
         return (dx1, dx2, dw, nb.dbias, nb.dgamma, nb.dbeta) + (None,) * 8
 
 
@@ -1052,11 +1118,19 @@ class PlainBlockHeadFn(torch.autograd.Function):
             dl = dl.contiguous()
             st = _pix_strides(dl)
         w2 = head_w.detach().reshape(k1, cout).contiguous()
+        ni = ctx.needs_input_grad
+        need_w = any(ni[1:5]) or ni[6] or ni[7]
+        dy = torch.empty_like(y)
+        nl = None if nl_coefs is None else (nl_coefs, ctx.nl_slope)
+        if not need_w:  # frozen parameters: the norm backward with dz = W^T dl alone -- no head dW / db, no weight gradient, no claimed slice
+            nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope)
+            nb.head(dl, st, w2, dy)
+            dx1 = _block_dgrad(x1, None, weight, dy, 1, nl, False, True, False)[0] if ni[0] else None
+            return (dx1,) + (None,) * 10
         dwh, dbh = grad_dest(head_w), grad_dest(head_b)
         dwh = torch.empty((k1, cout), device=dev, dtype=torch.float32) if dwh is None else dwh
         dbh = torch.empty(k1, device=dev, dtype=torch.float32) if dbh is None else dbh
         nb = _NormBwd(y, coefs, ctx.mode, ctx.fixed, ctx.slope, (gamma, beta_p, bias_p))
-        dy = torch.empty_like(y)
         if FUSE_HEAD_W and lib().mia_head_w_supported(nb.dtype, cout, k1):
             # head dW / db and the block's norm-backward sums in ONE pass over (dl, y); then the apply pass with dz = W^T dl recomputed
             ws = torch.empty(n * nb.slabs * k1 * (cout + 1), device=dev, dtype=torch.float32)
@@ -1066,7 +1140,6 @@ class PlainBlockHeadFn(torch.autograd.Function):
             call("mia_head_norm_wgrad", _p(dl), _p(y), nb.dtype, _p(coefs[2]), _p(coefs[3]), _c_float(ctx.slope), _p(dwh), _p(dbh),
                  _p(ws), n, _c_i64(hw), cout, k1, _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), 0, _stream())
             nb.head(dl, st, w2, dy)
-        nl = None if nl_coefs is None else (nl_coefs, ctx.nl_slope)
         dw = _block_wgrad(nb, x1, None, weight, 1, nl, dy)
         dx1 = None
         if ctx.needs_input_grad[0]:
@@ -1097,14 +1170,15 @@ class ConvTranspose2x2Fn(torch.autograd.Function):
         dtype = _dt(x)
         n, h, w, cin = x.shape
         cout = weight.shape[1]
-        dbias = _take_colsum(dout)
-        if dbias is None:
-            dbias = colsum(dout)
-        dst = grad_dest(ctx.small[0])
-        if dst is not None:  # straight into the flat gradient slice (the hinted sums are a strided view of interleaved statistics)
-            call("mia_gather_f32", _p(dbias), _c_i64(dbias.stride(0)), _p(dst), dbias.numel(), _stream())
-            dbias = dst
-        dw = conv_wgrad(WGRAD_2S2, dout, None, x, weight.shape, cin, cout, out=grad_dest(weight))
+        dbias = dw = None
+        hinted = _take_colsum(dout)  # (taken in any case: a hint must not outlive its backward)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # (frozen parameters: neither)
+            dbias = hinted if hinted is not None else colsum(dout)
+            dst = grad_dest(ctx.small[0])
+            if dst is not None:  # straight into the flat gradient slice (the hinted sums are a strided view of interleaved statistics)
+                call("mia_gather_f32", _p(dbias), _c_i64(dbias.stride(0)), _p(dst), dbias.numel(), _stream())
+                dbias = dst
+            dw = conv_wgrad(WGRAD_2S2, dout, None, x, weight.shape, cin, cout, out=grad_dest(weight))
         dx = None
         if ctx.needs_input_grad[0]:
             wb, npad, kpad = pack_cache(weight).get(weight, dtype, n_from_d0=True)  # [tap][ci][co]
@@ -1153,6 +1227,12 @@ class HeadFn(torch.autograd.Function):
             st = _pix_strides(dl)
         w2 = weight.detach().reshape(k1, c0).contiguous()
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not need_w:  # frozen parameters: the input gradient alone, no weight kernels, no claimed slice
+            if dx is not None:
+                call("mia_head_bwd", _p(dl), _p(x), _dt(x), _p(w2), _p(dx), None, None, None, n, _c_i64(h * w), c0, k1,
+                     _c_i64(st[0]), _c_i64(st[1]), _c_i64(st[2]), 0, _stream())
+            return dx, None, None
         dw, db = grad_dest(weight), grad_dest(ctx.small[0])
         dw = torch.empty((k1, c0), device=x.device, dtype=torch.float32) if dw is None else dw
         db = torch.empty(k1, device=x.device, dtype=torch.float32) if db is None else db
@@ -1624,6 +1704,114 @@ class ConsistencyFn(torch.autograd.Function):
 ConsistencyFn.last_out = ConsistencyFn.last_kept = ConsistencyFn.last_keep = None
 
 
+# ------------------------------------------------------------------ virtual adversarial training (KL distance, noise, perturbation)
+class KLConsistencyFn(torch.autograd.Function):
+    """weight * KL(softmax(target) || softmax(logits)) / den between two fp32 logits tensors [B, K, H, W] (include/mia_hip.h:
+    mia_kl_fwd; csrc/vat.hip): one streaming pass each way.  Only `logits` gets a gradient.  `dyn` is None or a DEVICE fp32 tensor whose
+    first element is the weight, read when the kernels run; `den` is the divisor of the sum over pixels and classes (B * H * W for a
+    per-pixel mean, B for "batchmean").  `last_out` = {weight * L, L, weight} of the latest forward, on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, dyn, den: float):
+        _need_dev(logits, target, dyn)
+        logits, st, target, tt = _loss_logits_pair("KL consistency", logits, target.detach(),
+                                                   "KL consistency: target logits {b} and logits {a} differ")
+        b, k1, h, w = logits.shape
+        dyn = _dyn_arg("KL consistency", dyn, 1, False)
+        hw = h * w
+        dev = logits.device
+        slabs = _two_logits_slabs(hw)
+        words = max(lib().mia_kl_workspace(b, slabs), 0)  # < 0: a bad shape, reported by the call below
+        buf = torch.empty(words + 4, device=dev, dtype=torch.float32)  # workspace | out[3] | coef: one allocation, every word written
+        ws, out, coef = buf[:words], buf[words:words + 3], buf[words + 3:]
+        call("mia_kl_fwd", _p(logits), _p(target), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(st), *_strides_i64(tt),
+             ctypes.c_double(float(den)), slabs, _p(ws), _p(coef), _p(out), _stream())
+        ctx.save_for_backward(logits, target, coef)
+        ctx.dyn, ctx.st, ctx.tt = dyn, st, tt
+        KLConsistencyFn.last_out = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, coef = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl, gst, g = _loss_bwd_begin(logits, gout)
+        call("mia_kl_bwd", _p(logits), _p(target), _p(coef), _p(ctx.dyn), _p(g), _p(dl), b, _c_i64(h * w), k1, *_strides_i64(ctx.st),
+             *_strides_i64(ctx.tt), *_strides_i64(gst), _stream())
+        return dl, None, None, None
+
+
+KLConsistencyFn.last_out = None
+
+
+def vat_noise(shape, device) -> torch.Tensor:
+    """fp32 tensor of `shape` with values in U[-0.5, 0.5) from the library's Philox kernel (`mia_vat_noise`), keyed by the device
+    generator's (seed, offset) and advancing the offset on the host exactly as `dropout_mask` does: `torch.manual_seed` reproduces it."""
+    dev = torch.device(device)
+    out = torch.empty(tuple(shape), device=dev, dtype=torch.float32)
+    nb = int(shape[0])
+    per = out.numel() // max(nb, 1)
+    gen = torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
+    seed, off = int(gen.initial_seed()), int(gen.get_offset())
+    gen.set_offset(off + 4 * ((out.numel() + 3) // 4))
+    call("mia_vat_noise", _p(out), nb, _c_i64(per), ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_uint64(off), _stream())
+    return out
+
+
+def sample_sumsq(x: torch.Tensor) -> torch.Tensor:
+    """[B] fp32: the sum of squares of every sample of a contiguous fp32 tensor [B, ...] (`mia_sample_sumsq`: double, rounded once)."""
+    _need_dev(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise MiaError("sample_sumsq: a contiguous fp32 tensor expected")
+    nb = x.shape[0]
+    per = x.numel() // max(nb, 1)
+    words = max(lib().mia_sample_sumsq_workspace(nb, _c_i64(per)), 0)
+    ws = torch.empty(words, device=x.device, dtype=torch.float32)
+    out = torch.empty(nb, device=x.device, dtype=torch.float32)
+    call("mia_sample_sumsq", _p(x), nb, _c_i64(per), _p(ws), _p(out), _stream())
+    return out
+
+
+def vat_perturb(x: torch.Tensor, g: torch.Tensor, sumsq: torch.Tensor, gscale: float, scale: float = 1.0,
+                scale_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x + s * (gscale * g) / (gscale * sqrt(sumsq[n]) + 1e-8) per sample n (`mia_vat_perturb`); s = `scale_dev[0]` (a device fp32
+    value read when the kernel runs) when given, else `scale`.  x, g: contiguous fp32 of one shape [B, ...]; sumsq: [B] fp32."""
+    _need_dev(x, g, sumsq, scale_dev)
+    for t in (x, g, sumsq):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise MiaError("vat_perturb: contiguous fp32 tensors expected")
+    if g.shape != x.shape or sumsq.numel() != x.shape[0]:
+        raise MiaError(f"vat_perturb: x {tuple(x.shape)}, g {tuple(g.shape)}, sumsq {tuple(sumsq.shape)} do not match")
+    if scale_dev is not None and (scale_dev.dtype != torch.float32 or scale_dev.numel() < 1):
+        raise MiaError("vat_perturb: a device `scale_dev` is one fp32 value")
+    nb = x.shape[0]
+    out = torch.empty_like(x)
+    call("mia_vat_perturb", _p(x), _p(g), _p(sumsq), _c_float(gscale), _c_float(scale), _p(scale_dev), _p(out), nb,
+         _c_i64(x.numel() // max(nb, 1)), _stream())
+    return out
+
+
+class frozen_parameters:
+    """Context manager: every parameter of `model` has `requires_grad == False` inside and its earlier setting back on every exit
+    path.  A forward AND its backward inside it (e.g. `torch.autograd.grad(loss, image)`) compute input gradients only: autograd
+    records at forward time which inputs need a gradient, and the backward nodes of this file then launch no weight-gradient kernel, claim no `grad_dest` slice and return None for their parameters."""
+
+    def __init__(self, model):
+        self.model, self._saved = model, None
+
+    def __enter__(self):
+        self._saved = [(p, p.requires_grad) for p in self.model.parameters()]
+        for p, _ in self._saved:
+            p.requires_grad_(False)
+        return self.model
+
+    def __exit__(self, *exc):
+        for p, r in self._saved:
+            p.requires_grad_(r)
+        self._saved = None
+        return False
+
+
 def ema_update(teacher_flat: torch.Tensor, student_flat: torch.Tensor, alpha) -> None:
     """teacher_flat = alpha * teacher_flat + (1 - alpha) * student_flat in place over flat fp32 buffers (include/mia_hip.h:
     mia_ema_update); `alpha` is a float in [0, 1] or a DEVICE fp32 tensor of one element read when the kernel runs.  alpha == 0
@@ -1963,7 +2151,11 @@ class PointwiseNormFn(torch.autograd.Function):
         dy = torch.empty_like(y)
         nb.plain(dz, None, dy)
         w4 = PointwiseNormFn._as_taps(weight, ctx.stride)
-        if ctx.stride == 2:
+        need_w = any(ctx.needs_input_grad[1:5])  # (frozen parameters: no weight gradient)
+        dw = None
+        if not need_w:
+            pass
+        elif ctx.stride == 2:
             g4 = conv_wgrad(WGRAD_2S2, x, None, dy, w4.shape, cout, cin)
             dw = g4[:, :, 0:1, 0:1].contiguous()
         else:  # 1x1 stride 1: centre tap of the 3x3 weight-gradient kernel
@@ -1976,6 +2168,8 @@ class PointwiseNormFn(torch.autograd.Function):
                 dx, _, _ = conv_mma(CONV_T2S2, dy, None, wb, npad, kpad, False, None, cin, (x.shape[1], x.shape[2]))
             else:
                 dx, _, _ = conv_mma(CONV_G1, dy, None, wb, npad, kpad, False, None, cin, (ho, wo))
+        if not need_w:
+            return dx, None, None, None, None, None, None
         return dx, dw, nb.dbias, nb.dgamma, nb.dbeta, None, None
 
 

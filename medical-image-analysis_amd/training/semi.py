@@ -27,6 +27,12 @@ convention, same device-resident schedule buffer `dyn`; it runs eagerly on one r
 initialisation, both trained, each on the supervised loss plus cross-entropy on the other's hard pseudo-labels
 (`losses.cross_pseudo.CrossPseudoSupervisionLoss`, csrc/cps.hip).  One `backward()` feeds two `FlatOptimizer`s.  Same batch
 convention and `dyn = {weight, confidence threshold}`; eager, one rank, 2-D inputs.  Out of scope: CutMix-CPS, Dice on pseudo-labels.
+
+`VATEngine` is virtual adversarial training (VAT: Miyato et al., TPAMI 2018), the one semi-supervised method the reference itself ships
+(`losses/adv_loss.py`): one network, no teacher.  The unlabelled images are pushed `eps` along the direction that changes the
+network's own prediction most -- found by a power iteration on the gradient of a KL distance with respect to the IMAGE
+(`losses.vat_loss.VATLoss`, csrc/vat.hip, csrc/stem_dgrad.hip) -- and the network is asked to predict there what it predicts on the
+clean image.  Same batch convention, `dyn = {weight, eps}`; eager, one rank, 2-D inputs.
 """
 from __future__ import annotations
 
@@ -447,3 +453,56 @@ class CPSEngine(SemiEngine):
                 checkpoint.optimizer_state_from_torch(self.optimizer_b, self.model_b, sd["optimizer"])
         ops.bump_param_epoch()  # packed weights of both networks are stale now
         return out
+
+
+class VATEngine(SemiEngine):
+    """one network + supervised loss on the labelled images + virtual adversarial training on the unlabelled ones + flat optimizer +
+    poly LR.  `train_step` returns the loss TENSOR (no host sync); `last_supervised` and `last_vat` (unweighted) are device by-products
+    of the latest step.  Per step, with lb = labeled_bs:
+
+        z_clean = model(image[lb:])                         no gradient, batch-norm running statistics untouched
+        x_adv   = vat.adversarial(model, image[lb:], z_clean, eps_dev=dyn[1:2])
+        out     = model(cat([image[:lb], x_adv]))           ONE training forward, after the power pass has finished: `UNet.forward`
+                                                            drops the producer -> consumer hints of the forward before it
+        loss    = supervised_loss(out[:lb], label[:lb]) + vat(out[lb:], z_clean, dyn=dyn)
+
+    With no unlabelled image or `vat=False` the engine forwards `image[:lb]` only and returns the supervised loss.
+    vat: None = `VATLoss()`; a module with that interface; False = no adversarial term.
+    vat_weight, eps: a float or an object with `.step(i)`; each step the engine writes `weight_i` and `eps_i` into the device buffer
+    `dyn` before anything reads it, outside the autograd graph.  eps None = the `eps` of `vat`.
+    The checkpoint is the base engine's: there is no extra state."""
+
+    def __init__(self, model, supervised_loss, labeled_bs: int, vat=None, vat_weight=1.0, eps=None, optimizer_name: str = "adam",
+                 optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250,
+                 lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.supervised_loss = supervised_loss
+        if vat is None:
+            from losses.vat_loss import VATLoss
+            vat = VATLoss()
+        self.vat = vat or None
+        self.vat_weight = vat_weight
+        self.eps = eps if eps is not None else (self.vat.eps if self.vat is not None else 0.0)
+        self.last_supervised = self.last_vat = None
+
+    def _dyn_values(self):
+        return _ramp_value(self.vat_weight, self.current_iter), _ramp_value(self.eps, self.current_iter)
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        lb = self.labeled_bs
+        if self.vat is None or image.shape[0] <= lb:
+            sup = self.supervised_loss(self.model(image[:lb]), label[:lb])
+            self.last_supervised = sup.detach()
+            return sup
+        self._write_dyn()
+        unlabeled = image[lb:]
+        with torch.no_grad(), ops.no_bn_tracking():
+            z_clean = self.model(unlabeled)
+        x_adv = self.vat.adversarial(self.model, unlabeled, z_clean, eps_dev=self.dyn[1:2])
+        out = self.model(torch.cat([image[:lb], x_adv]))
+        sup = self.supervised_loss(out[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        loss = sup + self.vat(out[lb:], z_clean, dyn=self.dyn)
+        self.last_vat = getattr(self.vat, "last_value", None)
+        return loss
