@@ -701,6 +701,37 @@ int mia_cps_fwd(const float* za, const float* zb, const float* dyn_dev, int nb, 
 int mia_cps_bwd(const float* za, const float* zb, const unsigned char* code, const float* dyn_dev, const float* grad_out, float* dza,
                 float* dzb, int nb, int64_t hw, int k1, int64_t asn, int64_t ask, int64_t asp, int64_t bsn, int64_t bsk, int64_t bsp,
                 int64_t gasn, int64_t gask, int64_t gasp, int64_t gbsn, int64_t gbsk, int64_t gbsp, void* stream);
+/* Bidirectional copy-paste (csrc/bcp.hip; BCP: Bai et al., CVPR 2023; the reference has no such code; definition:
+ * losses/copy_paste.py).
+ * Mix: out[n][c][p] = mask[n][p] != 0 ? fg[n][c][p] : bg[n][c][p] over contiguous fp32 [nb][c][hw] batches; mask: bytes, image n at
+ * mask + n * mask_sn with mask_sn == hw (one mask per image) or 0 (one mask for the batch); out: image n at out + n * out_sn, out_sn
+ * >= c * hw (a batch slice of a larger contiguous tensor).  A selection, not a blend: the bits of the chosen operand pass through
+ * (NaN payloads, -0.0).  16-byte accesses when hw % 4 == 0, fg / bg / out are 16-byte and mask 4-byte aligned and out_sn % 4 == 0; one
+ * element per thread otherwise; both give the same bits. */
+int mia_bcp_mix(const float* fg, const float* bg, const unsigned char* mask, float* out, int nb, int c, int64_t hw, int64_t mask_sn,
+                int64_t out_sn, void* stream);
+/* Two-source loss of a mixed image: logits fp32 by (sn, sk, sp) like mia_cps_fwd, 1 <= k1 <= 8; label_a, label_b: contiguous [nb][hw]
+ * index maps, both int64 or (labels_u8) both uint8; mask as for the mix.  Region A (mask != 0) reads label_a, region B label_b; a pixel
+ * reads ONLY its own region's label.  Per region r, over all images and pixels of the call, with p = softmax(z):
+ *   I_rk = sum p_k [y_r = k], Z_rk = sum p_k^2, Y_rk = sum [y_r = k], N_r = pixels of r (Y, N exact integers)
+ *   D_r = (1/k1) sum_k (1 - (2 I_rk + smooth) / (Z_rk + Y_rk + smooth)),  C_r = sum (logsumexp(z) - z[y_r]) / (N_r + 1e-16)
+ *   an empty region: D_r = C_r = 0.   L = weight_a (D_A + C_A) / 2 + weight_b (D_B + C_B) / 2
+ * out[5] = {L, D_A, C_A, D_B, C_B}; counts[2] = {N_A, N_B}; coef[2 (2 k1 + 1)]: what the backward reads.  A selected label outside
+ * [0, k1) follows mia_seg_loss_fwd: NaN out / coef and the sticky verdict in bad_label[1] (bad_label: the int32[2] of the other
+ * losses).  The backward recomputes the soft-max and writes dlogits = grad_out * dL/dz by (gsn, gsk, gsp) (grad_out: device pointer
+ * to one float or NULL for 1).  A thread owns the same four consecutive pixels on the 16-byte path (planar / channels-last logits, hw
+ * % 4 == 0, 16-byte aligned logits and int64 labels, 4-byte aligned uint8 labels and mask; dlogits in the layout class of the logits)
+ * and on the scalar path, and every sum runs in one fixed order: the two paths give the same bits, and every result is bit-identical
+ * from run to run (no float atomics).  slabs = blocks per image of the forward; workspace: mia_bcp_loss_workspace 4-byte words.
+ * Limits: nb * hw < 2^31.  Every check happens before any launch; nothing synchronises with the host. */
+int mia_bcp_loss_workspace(int nb, int k1, int slabs); /* 4-byte words; < 0 for a bad shape */
+int mia_bcp_loss_fwd(const float* logits, const void* label_a, const void* label_b, const unsigned char* mask, int nb, int64_t hw,
+                     int k1, int64_t sn, int64_t sk, int64_t sp, int64_t mask_sn, int labels_u8, float smooth, float weight_a,
+                     float weight_b, int slabs, float* workspace, float* coef, float* out, long long* counts, int* bad_label,
+                     void* stream);
+int mia_bcp_loss_bwd(const float* logits, const void* label_a, const void* label_b, const unsigned char* mask, const float* coef,
+                     const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
+                     int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, int labels_u8, void* stream);
 
 /* ------------------------------------------------------------------ virtual adversarial training (csrc/vat.hip) */
 /* KL distance between two fp32 logits tensors [nb][k1][hw], each addressed by its own (sn, sk, sp) / (tsn, tsk, tsp) element strides

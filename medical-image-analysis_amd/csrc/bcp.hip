@@ -1,0 +1,468 @@
+// Bidirectional copy-paste on the GPU (gfx950): the mix of two image batches under a mask, and the loss of a mixed image whose pixels
+// are supervised by one of TWO label maps (BCP: Bai et al., CVPR 2023).  The reference has no such code; the definition is
+// losses/copy_paste.py.
+//
+// Mix: out[n][c][p] = mask[n or 0][p] != 0 ? fg[n][c][p] : bg[n][c][p].  A SELECTION, not fg * m + bg * (1 - m): the 32 bits of the
+// chosen operand pass through as they are (NaN payloads and -0.0 included), and the operand not chosen is never looked at.
+//
+// Loss: logits z [nb][k1][hw] fp32 by (sn, sk, sp), label maps ya, yb [nb][hw] (int64 or uint8), mask byte m per pixel; region A is
+// m != 0 and reads ya, region B is m == 0 and reads yb.  With p = softmax(z), for each region r over ALL images and pixels of the call
+//   I_rk = sum m_r p_k [y_r = k]   Z_rk = sum m_r p_k^2   Y_rk = sum m_r [y_r = k]   N_r = sum m_r        (Y, N exact integers)
+//   D_r = (1/K) sum_k (1 - (2 I_rk + s) / (Z_rk + Y_rk + s))       every class counts, background included
+//   C_r = sum m_r (logsumexp(z) - z[y_r]) / (N_r + 1e-16)           an empty region: D_r = C_r = 0
+//   L = wa (D_A + C_A) / 2 + wb (D_B + C_B) / 2
+//   out = {L, D_A, C_A, D_B, C_B};  counts = {N_A, N_B}
+//   dL/dz_j = (w_r/2) [ (p_j - [j = y_r]) / (N_r + 1e-16) + p_j (g_rj - sum_k g_rk p_k) ],  g_rk = al_rk [y_r = k] + be_rk p_k,
+//   al_rk = -2 / (K den_rk), be_rk = 2 (2 I_rk + s) / (K den_rk^2), den_rk = Z_rk + Y_rk + s
+//   coef [2][2 k1 + 1] = per region {(w_r/2) al_rk}, {(w_r/2) be_rk}, (w_r/2) / (N_r + 1e-16): what the backward reads
+//   bcp_loss_fwd_kernel   block (image, slab of pixels): ONE streaming pass over logits, mask byte and the two label maps; the soft-max
+//                         in double per pixel (cs_softmax); a pixel adds into its own region's sums by predication; per-block partials
+//                         through LossBlockSums as (hi, lo) float pairs (loss_split) and ints
+//   bcp_finalize_kernel   one block: the partials in a fixed order in double / int64 (loss_totals, once per region) -> out, counts, coef
+//   bcp_loss_bwd_kernel   one streaming pass, a thread per pixel group: recomputes the soft-max, picks the region's coefficients by
+//                         the mask byte, writes dlogits by its own strides
+// A pixel reads ONLY its own region's label: the other map may hold anything there.  A selected label outside [0, k1) follows the
+// protocol of the other losses (loss_bad_label_verdict): NaN results and the sticky per-device verdict.
+// A thread owns the SAME four consecutive pixels on the 16-byte path (planar / channels-last logits, hw % 4 == 0, aligned pointers
+// and strides) and on the scalar path, and every sum runs in the same order on both, so the two paths give the same bits.  No float
+// atomics: bit-identical from run to run.  Nothing synchronises with the host.
+#include "pixel_stream.h"
+
+// ---------------------------------------------------------------- mix
+// WIDE: a thread owns four consecutive pixels of one (image, channel) plane: two 16-byte loads, one 4-byte mask load, one 16-byte store
+template <bool WIDE>
+__global__ __launch_bounds__(256) void bcp_mix_kernel(const unsigned* __restrict__ fg, const unsigned* __restrict__ bg,
+                                                      const unsigned char* __restrict__ mask, unsigned* __restrict__ out, int64_t hw,
+                                                      int64_t chw, int64_t msn, int64_t osn, int64_t total) {
+  constexpr int PX = WIDE ? 4 : 1;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t per = chw / PX, n = idx / per, e = (idx - n * per) * PX, p = e % hw;
+  const unsigned char* mk = mask + n * msn + p;
+  if constexpr (WIDE) {
+    const u32x4 f = *reinterpret_cast<const u32x4*>(fg + n * chw + e), b = *reinterpret_cast<const u32x4*>(bg + n * chw + e);
+    const unsigned m = *reinterpret_cast<const unsigned*>(mk);
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = ((m >> (8 * i)) & 0xffu) ? f[i] : b[i];
+    *reinterpret_cast<u32x4*>(out + n * osn + e) = o;
+    store_data_pad();
+  } else {
+    out[n * osn + e] = mk[0] ? fg[n * chw + e] : bg[n * chw + e];
+  }
+}
+
+// ---------------------------------------------------------------- loss: what forward and backward share
+// class index in [0, K1), -1 = outside
+template <int K1>
+__device__ __forceinline__ int bcp_class(unsigned lo, unsigned hi) {
+  return (hi == 0u && lo < (unsigned)K1) ? (int)lo : -1;
+}
+
+// the mask bytes of the group's pixels as flags in bits 0, 8, 16, 24 ... kept as the bytes themselves: a pixel tests its byte != 0
+template <bool WIDE>
+__device__ __forceinline__ unsigned bcp_mask_bytes(const unsigned char* __restrict__ mk, int nlive) {
+  if (WIDE) return *reinterpret_cast<const unsigned*>(mk);
+  unsigned m = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nlive) m |= (unsigned)mk[i] << (8 * i);
+  return m;
+}
+
+// the SELECTED label of each pixel of the group as a class index (-1: outside [0, K1), and every pixel past nlive)
+template <int K1, bool WIDE>
+__device__ __forceinline__ void bcp_labels(const long long* __restrict__ la, const long long* __restrict__ lb, unsigned mbytes,
+                                           int nlive, int (&y)[4]) {
+  if (WIDE) {
+    unsigned alo[4], ahi[4], blo[4], bhi[4];
+    load_label_quad(la, alo, ahi);
+    load_label_quad(lb, blo, bhi);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool m = ((mbytes >> (8 * i)) & 0xffu) != 0u;
+      y[i] = bcp_class<K1>(m ? alo[i] : blo[i], m ? ahi[i] : bhi[i]);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      y[i] = -1;
+      if (i < nlive) {
+        const unsigned long long v = (unsigned long long)((((mbytes >> (8 * i)) & 0xffu) != 0u) ? la[i] : lb[i]);
+        y[i] = bcp_class<K1>((unsigned)(v & 0xFFFFFFFFull), (unsigned)(v >> 32));
+      }
+    }
+  }
+}
+template <int K1, bool WIDE>
+__device__ __forceinline__ void bcp_labels(const unsigned char* __restrict__ la, const unsigned char* __restrict__ lb, unsigned mbytes,
+                                           int nlive, int (&y)[4]) {
+  if (WIDE) {
+    const unsigned wa = *reinterpret_cast<const unsigned*>(la), wb = *reinterpret_cast<const unsigned*>(lb);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool m = ((mbytes >> (8 * i)) & 0xffu) != 0u;
+      y[i] = bcp_class<K1>(((m ? wa : wb) >> (8 * i)) & 0xffu, 0u);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      y[i] = -1;
+      if (i < nlive) y[i] = bcp_class<K1>((((mbytes >> (8 * i)) & 0xffu) != 0u) ? la[i] : lb[i], 0u);
+    }
+  }
+}
+
+// the logits of the group's four pixels from pixel p; the scalar path reads the live ones one by one and zeroes the rest
+template <int K1, int MODE>
+__device__ __forceinline__ void bcp_load(const float* __restrict__ img, int64_t p, int nlive, const LossGeom& g, float (&v)[4][K1]) {
+  if constexpr (MODE != CS_SCALAR) {
+    cs_load<K1, MODE>(img, p, g, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float t[1][K1];
+#pragma unroll
+      for (int k = 0; k < K1; ++k) t[0][k] = 0.f;
+      if (i < nlive) cs_load<K1, CS_SCALAR>(img, p + i, g, t);
+#pragma unroll
+      for (int k = 0; k < K1; ++k) v[i][k] = t[0][k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------- forward
+template <int K1>
+struct BcpAcc {
+  double si[2][K1], sz[2][K1], ce[2];
+  int cy[2][K1], cn[2];
+};
+
+// one pixel: `in_a` / `in_b` say which region it adds to (neither: a pixel past the end of the image).  Every index into the
+// accumulators is a constant; the region is chosen by predication, so no register array is indexed at run time.
+template <int K1>
+__device__ __forceinline__ void bcp_fwd_pixel(const float (&v)[K1], int y, bool in_a, bool in_b, BcpAcc<K1>& a) {
+  float mx = v[0];
+#pragma unroll
+  for (int k = 1; k < K1; ++k) mx = fmaxf(mx, v[k]);
+  double p[K1];
+  cs_softmax<K1>(v, p);
+  double pmax = p[0];
+#pragma unroll
+  for (int k = 1; k < K1; ++k) pmax = p[k] > pmax ? p[k] : pmax;
+  // logsumexp(v) - v[y] = -log(max_k p_k) + (max v - v[y]) (cps.hip: cps_term); v[y] as a sum of one value and K1 - 1 zeros
+  float vy = 0.f;
+#pragma unroll
+  for (int k = 0; k < K1; ++k) vy += (k == y) ? v[k] : 0.f;
+  const double term = y >= 0 ? -log(pmax) + ((double)mx - (double)vy) : 0.0;
+  a.ce[0] += in_a ? term : 0.0;
+  a.ce[1] += in_b ? term : 0.0;
+  a.cn[0] += in_a;
+  a.cn[1] += in_b;
+#pragma unroll
+  for (int k = 0; k < K1; ++k) {
+    const bool t = y == k;
+    const double q = p[k] * p[k];
+    a.si[0][k] += (in_a && t) ? p[k] : 0.0;
+    a.si[1][k] += (in_b && t) ? p[k] : 0.0;
+    a.sz[0][k] += in_a ? q : 0.0;
+    a.sz[1][k] += in_b ? q : 0.0;
+    a.cy[0][k] += in_a && t;
+    a.cy[1][k] += in_b && t;
+  }
+}
+
+// the wave's sum of v in double, parked by lane 0 as a (hi, lo) pair in the block's slots
+template <int NF, int NI>
+__device__ __forceinline__ void bcp_park(const LossBlockSums<NF, NI>& red, int slot, double v) {
+  float pr[2];
+  loss_split(wave_sum_d(v), pr);
+  if (red.l == 0) { red.f[red.w][slot] = pr[0]; red.f[red.w][slot + 1] = pr[1]; }
+}
+
+// block (image, slab of `per` pixels; per % 4 == 0).  Per region r the block's slice of the workspace holds wf_r [2 K1 + 1][2]: the
+// (hi, lo) pairs of I_rk, Z_rk, CE_r, and wn_r [K1 + 1]: Y_rk, N_r.
+template <int K1, int MODE, typename LT>
+__global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restrict__ z, const LT* __restrict__ la,
+                                                           const LT* __restrict__ lb, const unsigned char* __restrict__ mask,
+                                                           int64_t hw, int64_t msn, LossGeom g, int slabs, int64_t per,
+                                                           float* __restrict__ ws, int nparts, int* __restrict__ bad_label) {
+  constexpr bool WIDE = MODE != CS_SCALAR;
+  constexpr int NQ = 2 * K1 + 1, NC = K1 + 1;
+  const int b = blockIdx.x / slabs, s = blockIdx.x % slabs;
+  const int64_t r0 = s * per, r1 = r0 + per < hw ? r0 + per : hw;
+  const float* img = z + b * g.sn;
+  const unsigned char* mk = mask + b * msn;
+  const LT* ia = la + (int64_t)b * hw;
+  const LT* ib = lb + (int64_t)b * hw;
+  BcpAcc<K1> acc;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    acc.ce[r] = 0.0;
+    acc.cn[r] = 0;
+#pragma unroll
+    for (int k = 0; k < K1; ++k) { acc.si[r][k] = 0.0; acc.sz[r][k] = 0.0; acc.cy[r][k] = 0; }
+  }
+  bool bad = false;
+  for (int64_t p = r0 + (int64_t)threadIdx.x * 4; p < r1; p += 256 * 4) {
+    const int nlive = r1 - p < 4 ? (int)(r1 - p) : 4;  // 4 on the 16-byte path (hw % 4 == 0)
+    float v[4][K1];
+    int y[4];
+    bcp_load<K1, MODE>(img, p, nlive, g, v);
+    const unsigned mb = bcp_mask_bytes<WIDE>(mk + p, nlive);
+    bcp_labels<K1, WIDE>(ia + p, ib + p, mb, nlive, y);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool live = i < nlive, m = ((mb >> (8 * i)) & 0xffu) != 0u;
+      bad |= live && y[i] < 0;
+      bcp_fwd_pixel<K1>(v[i], y[i], live && m, live && !m, acc);
+    }
+  }
+  if (bad) *bad_label = 1;
+  auto red = loss_block_sums<2 * 2 * NQ, 2 * NC>();
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      bcp_park(red, (r * NQ + k) * 2, acc.si[r][k]);
+      bcp_park(red, (r * NQ + K1 + k) * 2, acc.sz[r][k]);
+      const int c = wave_sum_i(acc.cy[r][k]);
+      if (red.l == 0) red.i[red.w][r * NC + k] = c;
+    }
+    bcp_park(red, (r * NQ + 2 * K1) * 2, acc.ce[r]);
+    const int c = wave_sum_i(acc.cn[r]);
+    if (red.l == 0) red.i[red.w][r * NC + K1] = c;
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 4 * NQ) {  // region t / (2 NQ), word t % (2 NQ) of this block's pairs
+    const int r = t / (2 * NQ), j = t % (2 * NQ);
+    ws[((size_t)r * nparts + blockIdx.x) * (2 * NQ) + j] = red.sum_f(t);
+  } else if (t >= 128 && t < 128 + 2 * NC) {
+    const int r = (t - 128) / NC, j = (t - 128) % NC;
+    int* wn = reinterpret_cast<int*>(ws + (size_t)2 * nparts * (2 * NQ));
+    wn[((size_t)r * nparts + blockIdx.x) * NC + j] = red.sum_i(t - 128);
+  }
+}
+
+// one block of 256 threads: out[5], counts[2], coef[2][2 K1 + 1]
+template <int K1>
+__global__ __launch_bounds__(256) void bcp_finalize_kernel(const float* __restrict__ ws, int nparts, float smooth, float wa, float wb,
+                                                           float* __restrict__ out, long long* __restrict__ counts,
+                                                           float* __restrict__ coef, int* __restrict__ bad_label) {
+  constexpr int NQ = 2 * K1 + 1, NC = K1 + 1;
+  __shared__ double tf[2][NQ], term[2][2];
+  __shared__ long long tn[2][NC];
+  __shared__ float res[5], cf[2 * NQ];  // results and coefficients are parked here and leave by one 4-byte store per lane
+  const int* wn = reinterpret_cast<const int*>(ws + (size_t)2 * nparts * (2 * NQ));
+  const int t = threadIdx.x;
+  for (int r = 0; r < 2; ++r) {  // the same LDS serves both regions: the totals are copied out before the second pass
+    const LossTotals tot = loss_totals<NQ, NC>(ws + (size_t)r * nparts * (2 * NQ), wn + (size_t)r * nparts * NC, nparts, NQ);
+    if (t < NQ) tf[r][t] = tot.f[t];
+    else if (t >= 64 && t < 64 + NC) tn[r][t - 64] = tot.n[t - 64];
+    __syncthreads();
+  }
+  if (t < 2) {  // one thread per region
+    const int r = t;
+    const double n = (double)tn[r][K1], s = (double)smooth, hw_ = 0.5 * (double)(r ? wb : wa);
+    double d = 0.0, c = 0.0;
+    if (tn[r][K1] > 0) {
+      for (int k = 0; k < K1; ++k) {
+        const double num = 2.0 * tf[r][k] + s, den = tf[r][K1 + k] + (double)tn[r][k] + s;
+        d += 1.0 - num / den;
+        cf[r * NQ + k] = (float)(hw_ * (-2.0 / ((double)K1 * den)));
+        cf[r * NQ + K1 + k] = (float)(hw_ * (2.0 * num / ((double)K1 * den * den)));
+      }
+      d /= (double)K1;
+      c = tf[r][2 * K1] / (n + 1e-16);
+      cf[r * NQ + 2 * K1] = (float)(hw_ / (n + 1e-16));
+    } else {  // an empty region: no term, and no pixel reads these
+      for (int k = 0; k < NQ; ++k) cf[r * NQ + k] = 0.f;
+    }
+    term[r][0] = d;
+    term[r][1] = c;
+  }
+  __syncthreads();
+  if (t == 0) {
+    res[0] = (float)((double)wa * (term[0][0] + term[0][1]) * 0.5 + (double)wb * (term[1][0] + term[1][1]) * 0.5);
+    res[1] = (float)term[0][0];
+    res[2] = (float)term[0][1];
+    res[3] = (float)term[1][0];
+    res[4] = (float)term[1][1];
+  }
+  __syncthreads();
+  if (t < 5) out[t] = res[t];
+  else if (t >= 64 && t < 66) counts[t - 64] = tn[t - 64][K1];
+  else if (t >= 128 && t < 128 + 2 * NQ) coef[t - 128] = cf[t - 128];
+  const int bad = bad_label[0];  // read before the verdict re-arms it: out[3], out[4] lie past the three values it overwrites
+  loss_bad_label_verdict(bad_label, out, coef, 2 * NQ);
+  if (bad && t >= 3 && t < 5) out[t] = __builtin_nanf("");
+}
+
+// ---------------------------------------------------------------- backward
+// a thread per group of four pixels (`groups` per image); dz has the layout class of z on the 16-byte path
+template <int K1, int MODE, typename LT>
+__global__ __launch_bounds__(256) void bcp_loss_bwd_kernel(const float* __restrict__ z, const LT* __restrict__ la,
+                                                           const LT* __restrict__ lb, const unsigned char* __restrict__ mask,
+                                                           const float* __restrict__ coef, const float* __restrict__ gout,
+                                                           float* __restrict__ dz, int64_t hw, int64_t msn, int64_t groups,
+                                                           int64_t total, LossGeom g, LossGeom gd) {
+  constexpr bool WIDE = MODE != CS_SCALAR;
+  constexpr int NQ = 2 * K1 + 1;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t b = idx / groups, p = (idx - b * groups) * 4;
+  const int nlive = hw - p < 4 ? (int)(hw - p) : 4;
+  const double go = (double)(gout ? gout[0] : 1.f);
+  float ca[NQ], cb[NQ];  // uniform: the two regions' coefficients
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) { ca[k] = coef[k]; cb[k] = coef[NQ + k]; }
+  float v[4][K1], d[4][K1];
+  int y[4];
+  bcp_load<K1, MODE>(z + b * g.sn, p, nlive, g, v);
+  const unsigned mb = bcp_mask_bytes<WIDE>(mask + b * msn + p, nlive);
+  bcp_labels<K1, WIDE>(la + b * hw + p, lb + b * hw + p, mb, nlive, y);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bool m = ((mb >> (8 * i)) & 0xffu) != 0u;
+    double pr[K1], gk[K1], dot = 0.0;
+    cs_softmax<K1>(v[i], pr);
+#pragma unroll
+    for (int k = 0; k < K1; ++k) {
+      const double al = (double)(m ? ca[k] : cb[k]), be = (double)(m ? ca[K1 + k] : cb[K1 + k]);
+      gk[k] = (y[i] == k ? al : 0.0) + be * pr[k];
+      dot += gk[k] * pr[k];
+    }
+    const double cec = (double)(m ? ca[2 * K1] : cb[2 * K1]);
+#pragma unroll
+    for (int k = 0; k < K1; ++k) d[i][k] = (float)(go * (cec * (pr[k] - (y[i] == k ? 1.0 : 0.0)) + pr[k] * (gk[k] - dot)));
+  }
+  float* dst = dz + b * gd.sn;
+  if constexpr (WIDE) {
+    cs_store<K1, MODE>(dst, p, gd, d);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < nlive) {
+        float t[1][K1];
+#pragma unroll
+        for (int k = 0; k < K1; ++k) t[0][k] = d[i][k];
+        cs_store<K1, CS_SCALAR>(dst, p + i, gd, t);
+      }
+  }
+}
+
+// ---------------------------------------------------------------- host side
+template <int K1, int MODE>
+static void bcp_launch_fwd(hipStream_t st, const float* z, const void* la, const void* lb, bool u8, const unsigned char* mask, int nb,
+                           int64_t hw, int64_t msn, const LossGeom& g, int slabs, float* ws, int* bad_label) {
+  const int64_t per = ceil_div64(ceil_div64(hw, 4), slabs) * 4;
+  const dim3 grid((unsigned)(nb * slabs)), blk(256);
+  if (u8)
+    hipLaunchKernelGGL((bcp_loss_fwd_kernel<K1, MODE, unsigned char>), grid, blk, 0, st, z, static_cast<const unsigned char*>(la),
+                       static_cast<const unsigned char*>(lb), mask, hw, msn, g, slabs, per, ws, nb * slabs, bad_label);
+  else
+    hipLaunchKernelGGL((bcp_loss_fwd_kernel<K1, MODE, long long>), grid, blk, 0, st, z, static_cast<const long long*>(la),
+                       static_cast<const long long*>(lb), mask, hw, msn, g, slabs, per, ws, nb * slabs, bad_label);
+}
+
+template <int K1, int MODE>
+static void bcp_launch_bwd(hipStream_t st, const float* z, const void* la, const void* lb, bool u8, const unsigned char* mask,
+                           const float* coef, const float* gout, float* dz, int nb, int64_t hw, int64_t msn, const LossGeom& g,
+                           const LossGeom& gd) {
+  const int64_t groups = ceil_div64(hw, 4), total = (int64_t)nb * groups;
+  const dim3 grid((unsigned)ceil_div64(total, 256)), blk(256);
+  if (u8)
+    hipLaunchKernelGGL((bcp_loss_bwd_kernel<K1, MODE, unsigned char>), grid, blk, 0, st, z, static_cast<const unsigned char*>(la),
+                       static_cast<const unsigned char*>(lb), mask, coef, gout, dz, hw, msn, groups, total, g, gd);
+  else
+    hipLaunchKernelGGL((bcp_loss_bwd_kernel<K1, MODE, long long>), grid, blk, 0, st, z, static_cast<const long long*>(la),
+                       static_cast<const long long*>(lb), mask, coef, gout, dz, hw, msn, groups, total, g, gd);
+}
+
+template <int K1, int MODE>
+static void bcp_launch_finalize(hipStream_t st, const float* ws, int nparts, float smooth, float wa, float wb, float* out,
+                                long long* counts, float* coef, int* bad_label) {
+  hipLaunchKernelGGL(bcp_finalize_kernel<K1>, dim3(1), dim3(256), 0, st, ws, nparts, smooth, wa, wb, out, counts, coef, bad_label);
+}
+
+static inline bool bcp_al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
+// the 16-byte path: the logits' class, four pixels per unit in every map (labels as 16-byte units of int64 or 4-byte words of uint8,
+// the mask as 4-byte words)
+static int bcp_mode(const float* z, const LossGeom& g, int k1, int64_t hw, const void* la, const void* lb, bool u8,
+                    const unsigned char* mask) {
+  const int sm = cs_mode(z, g, k1);
+  if (sm == CS_SCALAR || hw % 4 != 0 || !bcp_al4(mask)) return CS_SCALAR;
+  if (u8 ? !(bcp_al4(la) && bcp_al4(lb)) : !(cs_al16(la) && cs_al16(lb))) return CS_SCALAR;
+  return sm;
+}
+
+static size_t bcp_words_per_block(int k1) { return (size_t)2 * ((2 * k1 + 1) * 2 + k1 + 1); }
+
+extern "C" int mia_bcp_mix(const float* fg, const float* bg, const unsigned char* mask, float* out, int nb, int c, int64_t hw,
+                           int64_t mask_sn, int64_t out_sn, void* stream) {
+  MIA_CHECK_ARG(fg && bg && mask && out, "mia_bcp_mix: null pointer");
+  MIA_CHECK_ARG(nb > 0 && c > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)c * hw <= 0x7fffffff &&
+                    ceil_div64((int64_t)nb * c * hw, 256) <= 0x7fffffff,
+                "mia_bcp_mix: bad shape nb=%d c=%d hw=%lld", nb, c, (long long)hw);
+  MIA_CHECK_ARG((mask_sn == 0 || mask_sn == hw) && out_sn >= (int64_t)c * hw, "mia_bcp_mix: bad strides mask_sn=%lld out_sn=%lld",
+                (long long)mask_sn, (long long)out_sn);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t chw = (int64_t)c * hw;
+  const bool wide = hw % 4 == 0 && out_sn % 4 == 0 && cs_al16(fg) && cs_al16(bg) && cs_al16(out) && bcp_al4(mask);
+  const int64_t total = (int64_t)nb * (wide ? chw / 4 : chw);
+  const dim3 grid((unsigned)ceil_div64(total, 256)), blk(256);
+  const unsigned* f = reinterpret_cast<const unsigned*>(fg);
+  const unsigned* b = reinterpret_cast<const unsigned*>(bg);
+  unsigned* o = reinterpret_cast<unsigned*>(out);
+  if (wide) hipLaunchKernelGGL(bcp_mix_kernel<true>, grid, blk, 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
+  else hipLaunchKernelGGL(bcp_mix_kernel<false>, grid, blk, 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+extern "C" int mia_bcp_loss_workspace(int nb, int k1, int slabs) {
+  if (nb <= 0 || slabs <= 0 || k1 < 1 || k1 > LOSS_MAXK || (int64_t)nb * slabs * (int64_t)bcp_words_per_block(k1) > 0x7fffffff) return -1;
+  return (int)((size_t)nb * slabs * bcp_words_per_block(k1));
+}
+
+extern "C" int mia_bcp_loss_fwd(const float* logits, const void* label_a, const void* label_b, const unsigned char* mask, int nb,
+                                int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t mask_sn, int labels_u8, float smooth,
+                                float weight_a, float weight_b, int slabs, float* workspace, float* coef, float* out,
+                                long long* counts, int* bad_label, void* stream) {
+  MIA_CHECK_ARG(logits && label_a && label_b && mask && workspace && coef && out && counts && bad_label,
+                "mia_bcp_loss_fwd: null pointer");
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_bcp_loss_fwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
+  MIA_CHECK_ARG(nb > 0 && hw > 0 && slabs > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff &&
+                    (int64_t)nb * slabs * (int64_t)bcp_words_per_block(k1) <= 0x7fffffff,
+                "mia_bcp_loss_fwd: bad shape nb=%d hw=%lld slabs=%d", nb, (long long)hw, slabs);
+  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && (mask_sn == 0 || mask_sn == hw), "mia_bcp_loss_fwd: bad strides");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const LossGeom g{sn, sk, sp};
+  const bool u8 = labels_u8 != 0;
+  const int sm = bcp_mode(logits, g, k1, hw, label_a, label_b, u8, mask);
+  CS_DISPATCH1(bcp_launch_fwd, st, logits, label_a, label_b, u8, mask, nb, hw, mask_sn, g, slabs, workspace, bad_label);
+  CS_DISPATCH1(bcp_launch_finalize, st, workspace, nb * slabs, smooth, weight_a, weight_b, out, counts, coef, bad_label);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+extern "C" int mia_bcp_loss_bwd(const float* logits, const void* label_a, const void* label_b, const unsigned char* mask,
+                                const float* coef, const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn,
+                                int64_t sk, int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, int labels_u8,
+                                void* stream) {
+  MIA_CHECK_ARG(logits && label_a && label_b && mask && coef && dlogits, "mia_bcp_loss_bwd: null pointer");
+  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_bcp_loss_bwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
+  MIA_CHECK_ARG(nb > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff, "mia_bcp_loss_bwd: bad shape nb=%d hw=%lld",
+                nb, (long long)hw);
+  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && gsn >= 0 && gsk >= 0 && gsp >= 0 && (mask_sn == 0 || mask_sn == hw),
+                "mia_bcp_loss_bwd: bad strides");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const LossGeom g{sn, sk, sp}, gd{gsn, gsk, gsp};
+  const bool u8 = labels_u8 != 0;
+  int sm = bcp_mode(logits, g, k1, hw, label_a, label_b, u8, mask);
+  if (cs_mode(dlogits, gd, k1) != sm) sm = CS_SCALAR;  // the gradient in the layout class of its logits, or one pixel at a time
+  CS_DISPATCH1(bcp_launch_bwd, st, logits, label_a, label_b, u8, mask, coef, grad_out, dlogits, nb, hw, mask_sn, g, gd);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}

@@ -108,3 +108,22 @@ static int cs_mode(const void* base, const LossGeom& g, int k1) {
     case 7: CS_MODES(FN, 7, __VA_ARGS__); break;        \
     default: CS_MODES(FN, 8, __VA_ARGS__); break;       \
   }
+
+// The same for a loss over ONE logits tensor (bcp.hip): FN<K1, SM>(args...) for the run-time (k1, sm)
+#define CS_MODES1(FN, K, ...)                                          \
+  do {                                                                 \
+    if (sm == CS_SCALAR) FN<K, CS_SCALAR>(__VA_ARGS__);                \
+    else if (sm == CS_PLANAR4) FN<K, CS_PLANAR4>(__VA_ARGS__);         \
+    else FN<K, CS_CLAST4>(__VA_ARGS__);                                \
+  } while (0)
+#define CS_DISPATCH1(FN, ...)                            \
+  switch (k1) {                                          \
+    case 1: CS_MODES1(FN, 1, __VA_ARGS__); break;        \
+    case 2: CS_MODES1(FN, 2, __VA_ARGS__); break;        \
+    case 3: CS_MODES1(FN, 3, __VA_ARGS__); break;        \
+    case 4: CS_MODES1(FN, 4, __VA_ARGS__); break;        \
+    case 5: CS_MODES1(FN, 5, __VA_ARGS__); break;        \
+    case 6: CS_MODES1(FN, 6, __VA_ARGS__); break;        \
+    case 7: CS_MODES1(FN, 7, __VA_ARGS__); break;        \
+    default: CS_MODES1(FN, 8, __VA_ARGS__); break;       \
+  }

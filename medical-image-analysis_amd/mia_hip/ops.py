@@ -254,6 +254,8 @@ class PackPlan:
                     self.split_bufs[i] = torch.empty(e[3].shape, device=e[3].device, dtype=torch.int32)
             self.split_descs = _split_descs([(e[3], self.split_bufs[i], self.amax_slots[i:i + 1]) for i, e in enumerate(self.entries)],
                                             self.entries[0][0].device)
+            # entry i's descriptor alone, for PackCache.get's per-tensor path: it must name the slot `plant` hangs on the buffer
+            self.entry_split_descs = list(self.split_descs.split(lib().mia_split_desc_bytes()))
 
     def valid(self) -> bool:
         return all(w.data_ptr() == ptr for w, _, _, _, _, _, ptr in self.entries)
@@ -273,6 +275,9 @@ class PackPlan:
             if self.amax_descs is not None:
                 buf._mia_amax = (self.amax_slots[i:i + 1], buf._version)
                 buf._mia_split = self.split_bufs[i]
+                # a later per-tensor re-pack (another optimizer moved the epoch on) scales by THIS slot: the descriptor made with the
+                # buffer's first slot would point at memory that slot no longer owns
+                buf._mia_split_desc = self.entry_split_descs[i]
 
 
 _caches = {}
@@ -1960,6 +1965,96 @@ def cps_decode(code: torch.Tensor):
     ops on whatever device `code` lives on -- for logging and tests, not the hot path."""
     c = code.to(torch.int64)
     return c & 7, (c >> 3) & 7, ((c >> 6) & 1).bool(), ((c >> 7) & 1).bool()
+
+
+# ------------------------------------------------------------------ bidirectional copy-paste (mix under a mask, two-source loss)
+BCP_MAX_CLASSES = 8
+
+
+def _bcp_mask(who: str, mask: torch.Tensor, b: int, h: int, w: int):
+    """(mask, image stride): a contiguous uint8 mask [H, W] (stride 0: one mask for the batch) or [B, H, W] (stride H * W)."""
+    if mask.dtype != torch.uint8 or tuple(mask.shape) not in ((h, w), (b, h, w)):
+        raise MiaError(f"{who}: the mask is uint8 [{h}, {w}] or [{b}, {h}, {w}], got {mask.dtype} {tuple(mask.shape)}")
+    return mask.contiguous(), (h * w if mask.ndim == 3 else 0)
+
+
+def bcp_mix(fg: torch.Tensor, bg: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[n, c, p] = fg[n, c, p] where mask[n or 0, p] != 0, else bg[n, c, p] (include/mia_hip.h: mia_bcp_mix; csrc/bcp.hip).
+    fg, bg: contiguous fp32 [B, C, H, W]; mask: uint8 [H, W] or [B, H, W]; out: None (a new tensor) or fp32 [B, C, H, W] whose
+    images are dense, e.g. a batch slice of a larger contiguous tensor.  A SELECTION, not `fg * m + bg * (1 - m)`: the bits of the
+    chosen operand pass through, NaN payloads and -0.0 included, and a NaN in the operand not chosen does not spread.  No gradient."""
+    _need_dev(fg, bg, mask, out)
+    if fg.ndim != 4 or bg.shape != fg.shape or fg.dtype != torch.float32 or bg.dtype != torch.float32 or \
+            not fg.is_contiguous() or not bg.is_contiguous():
+        raise MiaError(f"bcp_mix: two contiguous fp32 [B, C, H, W] batches of one shape expected, got {tuple(fg.shape)} {fg.dtype} "
+                       f"and {tuple(bg.shape)} {bg.dtype}")
+    b, c, h, w = fg.shape
+    mask, msn = _bcp_mask("bcp_mix", mask, b, h, w)
+    if out is None:
+        out = torch.empty_like(fg)
+    elif out.shape != fg.shape or out.dtype != torch.float32 or out.device != fg.device or \
+            out.stride()[1:] != fg.stride()[1:] or (b > 1 and out.stride(0) < c * h * w):
+        raise MiaError("bcp_mix: `out` is fp32 of the inputs' shape with dense images (a batch slice of a contiguous tensor)")
+    if fg.numel() == 0:
+        return out
+    call("mia_bcp_mix", _p(fg.detach()), _p(bg.detach()), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn),
+         _c_i64(out.stride(0) if b > 1 else c * h * w), _stream())
+    return out
+
+
+class CopyPasteLossFn(torch.autograd.Function):
+    """`apply(logits, label_a, label_b, mask, weight_a, weight_b, smooth)` -> the two-source loss of a copy-paste mixed batch
+    (include/mia_hip.h: mia_bcp_loss_fwd; csrc/bcp.hip; the definition is the module text of losses/copy_paste.py): a pixel is
+    supervised by `label_a` where `mask != 0` and by `label_b` elsewhere, each region with its own weight, its own squared-denominator
+    Dice over the whole call and its own mean cross-entropy.  One streaming forward pass and one streaming backward pass; only the
+    logits get a gradient.  fp32 logits [B, K, H, W], K <= 8, any layout whose H and W collapse; labels [B, H, W] int64 or uint8
+    (anything else, or a mixed pair, is converted to int64); mask uint8 [H, W] or [B, H, W].  By-products of the latest forward, on
+    the device: `last_out` = {L, D_A, C_A, D_B, C_B} and `last_counts` (int64 [2]: pixels of region A, of region B)."""
+
+    @staticmethod
+    def forward(ctx, logits, label_a, label_b, mask, weight_a: float, weight_b: float, smooth: float):
+        _need_dev(logits, label_a, label_b, mask)
+        if logits.ndim != 4:
+            raise NotImplementedError("the HIP copy-paste loss implements 2-D inputs [B, K, H, W]")
+        logits, st = _loss_logits(logits)
+        b, k1, h, w = logits.shape
+        if not 1 <= k1 <= BCP_MAX_CLASSES:
+            raise MiaError(f"copy-paste loss: {k1} classes not in [1, {BCP_MAX_CLASSES}] (the tensor-op form, fused=False, takes more)")
+        if label_a.numel() != b * h * w or label_b.numel() != b * h * w:
+            raise MiaError(f"copy-paste loss: labels {tuple(label_a.shape)} / {tuple(label_b.shape)} do not index the pixels of "
+                           f"logits {tuple(logits.shape)}")
+        u8 = label_a.dtype == torch.uint8 and label_b.dtype == torch.uint8
+        label_a, label_b = (t.reshape(b, h, w) if u8 else t.reshape(b, h, w).long() for t in (label_a, label_b))
+        label_a, label_b = label_a.contiguous(), label_b.contiguous()
+        mask, msn = _bcp_mask("copy-paste loss", mask, b, h, w)
+        hw = h * w
+        dev = logits.device
+        slabs = _two_logits_slabs(hw)
+        words = max(lib().mia_bcp_loss_workspace(b, k1, slabs), 0)  # < 0: a bad shape, reported by the call below
+        ncoef = 4 * k1 + 2
+        buf = torch.empty(words + ncoef + 5, device=dev, dtype=torch.float32)  # workspace | coef | out[5]: every word written
+        ws, coef, out = buf[:words], buf[words:words + ncoef], buf[words + ncoef:]
+        counts = torch.empty(2, device=dev, dtype=torch.int64)
+        bad = _bad_flags(dev)
+        call("mia_bcp_loss_fwd", _p(logits), _p(label_a), _p(label_b), _p(mask), b, _c_i64(hw), k1, *_strides_i64(st), _c_i64(msn),
+             int(u8), _c_float(smooth), _c_float(weight_a), _c_float(weight_b), slabs, _p(ws), _p(coef), _p(out), _p(counts), _p(bad),
+             _stream())
+        ctx.save_for_backward(logits, label_a, label_b, mask, coef)
+        ctx.st, ctx.msn, ctx.u8 = st, msn, u8
+        CopyPasteLossFn.last_out, CopyPasteLossFn.last_counts = out, counts
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, label_a, label_b, mask, coef = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl, gst, g = _loss_bwd_begin(logits, gout)
+        call("mia_bcp_loss_bwd", _p(logits), _p(label_a), _p(label_b), _p(mask), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1,
+             *_strides_i64(ctx.st), *_strides_i64(gst), _c_i64(ctx.msn), int(ctx.u8), _stream())
+        return dl, None, None, None, None, None, None
+
+
+CopyPasteLossFn.last_out = CopyPasteLossFn.last_counts = None
 
 
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)

@@ -8,7 +8,7 @@ the student's (`ops.ema_update`: ONE pass over `FlatOptimizer.flat_param`).  Wit
 by the entropy of the mean of T stochastic teacher passes (fresh input noise, fresh Dropout2d masks), accumulated by the
 prediction path's `mia_softmax_accum`.
 
-The three engines of this file derive from `SemiEngine`, which owns what they share on top of `training.engine.EngineBase`: the
+The engines of this file derive from `SemiEngine`, which owns what they share on top of `training.engine.EngineBase`: the
 batch convention and its checks, the schedule buffer `dyn` and the skeleton of `train_step`.  An engine adds its networks, its loss
 and what it does after the optimizer step; `TrainEngine` is not involved.
 
@@ -33,6 +33,13 @@ convention and `dyn = {weight, confidence threshold}`; eager, one rank, 2-D inpu
 network's own prediction most -- found by a power iteration on the gradient of a KL distance with respect to the IMAGE
 (`losses.vat_loss.VATLoss`, csrc/vat.hip, csrc/stem_dgrad.hip) -- and the network is asked to predict there what it predicts on the
 clean image.  Same batch convention, `dyn = {weight, eps}`; eager, one rank, 2-D inputs.
+
+`BCPEngine` is bidirectional copy-paste (BCP: Bai et al., CVPR 2023), the one method of those tables that mixes labelled and unlabelled
+images: a box of a labelled image is pasted into an unlabelled one and the other way round (`ops.bcp_mix`), and every pixel of a mixed
+image is supervised by the ground truth or by the EMA teacher's pseudo-label, whichever image it came from
+(`losses.copy_paste.CopyPasteLoss`, csrc/bcp.hip).  It shares the teacher machinery (`_EMATeacher`) with `MeanTeacherEngine`.  Eager,
+one rank, 2-D inputs, index labels.  Out of scope: CutMix-CPS (the mix kernel and the mask generator are what it would need), 3-D
+volumes, per-image masks in the engine (the kernels take them).
 """
 from __future__ import annotations
 
@@ -138,50 +145,15 @@ class SemiEngine(EngineBase):
         return loss.detach()
 
 
-class MeanTeacherEngine(SemiEngine):
-    """student + EMA teacher + supervised loss + consistency loss + flat optimizer + poly LR.  `train_step` returns the loss TENSOR
-    (no host sync); `last_supervised`, `last_consistency` (unweighted) and `last_kept` are device by-products of the latest step.
+class _EMATeacher:
+    """What the engines with an EMA teacher share (`MeanTeacherEngine`, `BCPEngine`), mixed in beside `SemiEngine`: the teacher's
+    parameters as views into `teacher_flat`, the EMA + re-pack after the optimizer step, prediction with either network, and the
+    teacher's file in a checkpoint.  The engine sets `self.teacher` and `self.ema_decay`, then calls `_init_teacher()`."""
 
-    teacher: a second `UNet` of the student's architecture.  Its trainable parameters become views into `teacher_flat`, a buffer
-    with the student's `FlatOptimizer` offsets, initialised bit for bit from the student; they never receive a gradient.  The teacher
-    stays in train mode during training (its Dropout2d masks are what makes the uncertainty passes stochastic, as in the published
-    code).
-    consistency: None = `SoftmaxMSEConsistency` for the student's classes; a module with that call signature; False = no teacher
-    pass and no consistency term (the EMA still runs).
-    consistency_weight, threshold_ramp: a float or an object with `.step(i)`; each step the engine writes
-    `weight_i` and `threshold_i = (0.75 + 0.25 * ramp_i) * ln(K)` into the device buffer `dyn` before anything reads it, outside
-    the autograd graph.  threshold_ramp None = 0, i.e. the schedule's strictest threshold `0.75 ln K` throughout.
-    uncertainty_passes: T extra teacher passes whose mean soft-max masks the consistency term; 0 = the plain Mean Teacher form.
-    noise_std, noise_clip: the teacher sees `image + clamp(N(0, noise_std^2), -noise_clip, noise_clip)`."""
-
-    _one_rank_why = " (the EMA and the teacher passes are not sharded yet)"
-
-    def __init__(self, model, teacher, supervised_loss, labeled_bs: int, ema_decay: float = 0.99, consistency=None,
-                 consistency_weight=0.1, uncertainty_passes: int = 0, threshold_ramp=None, noise_std: float = 0.1,
-                 noise_clip: float = 0.2, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
-                 start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
-                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
-        if not 0.0 <= ema_decay <= 1.0:
-            raise ValueError("MeanTeacherEngine: ema_decay must lie in [0, 1]")
-        if uncertainty_passes < 0:
-            raise ValueError("MeanTeacherEngine: uncertainty_passes must not be negative")
-        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
-                         lr_warmup_iter, lr_interval, lr_scheduler_name)
-        self.teacher = teacher
-        self.supervised_loss = supervised_loss
-        self.ema_decay = float(ema_decay)
-        self.uncertainty_passes = int(uncertainty_passes)
-        self.consistency_weight, self.threshold_ramp = consistency_weight, threshold_ramp
-        self.noise_std, self.noise_clip = float(noise_std), float(noise_clip)
-        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
-        if consistency is None:
-            from losses.consistency_loss import SoftmaxMSEConsistency
-            consistency = SoftmaxMSEConsistency(self.num_classes - 1)
-        self.consistency = consistency or None
+    def _init_teacher(self) -> None:
         self._adopt_teacher()
         self.ema_step = 0
         self._teacher_plan = None
-        self.last_supervised = self.last_consistency = self.last_kept = None
 
     def _nets(self):
         return (self.model, self.teacher)
@@ -192,7 +164,7 @@ class MeanTeacherEngine(SemiEngine):
         names = {id(p): n for n, p in self.model.named_parameters()}
         tparams = dict(self.teacher.named_parameters())
         if set(tparams) != set(names.values()) or any(tparams[names[id(p)]].shape != p.shape for p in opt.params):
-            raise ValueError("MeanTeacherEngine: the teacher must have the student's architecture (same parameter names and shapes)")
+            raise ValueError(f"{type(self).__name__}: the teacher must have the student's architecture (same parameter names and shapes)")
         self.teacher.to(opt.flat_param.device)
         self.teacher.load_state_dict(self.model.state_dict())  # buffers and frozen parameters; the trainable ones again below
         self.teacher_flat = torch.zeros_like(opt.flat_param)
@@ -208,45 +180,6 @@ class MeanTeacherEngine(SemiEngine):
         for t in self.teacher.parameters():
             t.requires_grad_(False)
         ops.bump_param_epoch()
-
-    def _dyn_values(self):
-        r = 0.0 if self.threshold_ramp is None else _ramp_value(self.threshold_ramp, self.current_iter)
-        return _ramp_value(self.consistency_weight, self.current_iter), entropy_threshold(r, self.num_classes)
-
-    def _noisy(self, x: torch.Tensor) -> torch.Tensor:
-        if self.noise_std == 0.0:
-            return x
-        return x + torch.clamp(torch.randn_like(x) * self.noise_std, -self.noise_clip, self.noise_clip)
-
-    @torch.no_grad()
-    def _teacher_passes(self, unlabeled: torch.Tensor):
-        """(zt, pbar): the teacher's logits on one noisy copy, and the mean soft-max of `uncertainty_passes` further stochastic passes
-        (None without them).  Runs BEFORE the student's forward: `UNet.forward` clears the producer -> consumer hints that belong to
-        the backward of the latest forward."""
-        zt = self.teacher(self._noisy(unlabeled))
-        pbar = None
-        if self.uncertainty_passes > 0:
-            from inference.predictor import softmax_accum
-            pbar = torch.empty(zt.shape, device=zt.device, dtype=torch.float32)
-            for i in range(self.uncertainty_passes):
-                softmax_accum(self.teacher(self._noisy(unlabeled)), pbar, None, weight=1.0 / self.uncertainty_passes, first=i == 0)
-        return zt, pbar
-
-    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
-        lb = self.labeled_bs
-        consistent = self.consistency is not None and image.shape[0] > lb
-        if consistent:
-            self._write_dyn()
-            zt, pbar = self._teacher_passes(image[lb:])
-        output = self.model(image)
-        sup = self.supervised_loss(output[:lb], label[:lb])
-        self.last_supervised = sup.detach()
-        if not consistent:
-            return sup
-        loss = sup + self.consistency(output[lb:], zt, pbar, dyn=self.dyn)
-        self.last_consistency = getattr(self.consistency, "last_value", None)
-        self.last_kept = getattr(self.consistency, "last_kept", None)
-        return loss
 
     def _after_step(self) -> None:
         """The EMA over the flat buffers, then the teacher's packed weight copies.  The optimizer step just before has moved the
@@ -289,6 +222,89 @@ class MeanTeacherEngine(SemiEngine):
             self.ema_step = int(sd["ema_step"])
         ops.bump_param_epoch()  # packed weights of both networks are stale now
         return out
+
+
+class MeanTeacherEngine(_EMATeacher, SemiEngine):
+    """student + EMA teacher + supervised loss + consistency loss + flat optimizer + poly LR.  `train_step` returns the loss TENSOR
+    (no host sync); `last_supervised`, `last_consistency` (unweighted) and `last_kept` are device by-products of the latest step.
+
+    teacher: a second `UNet` of the student's architecture.  Its trainable parameters become views into `teacher_flat`, a buffer
+    with the student's `FlatOptimizer` offsets, initialised bit for bit from the student; they never receive a gradient.  The teacher
+    stays in train mode during training (its Dropout2d masks are what makes the uncertainty passes stochastic, as in the published
+    code).
+    consistency: None = `SoftmaxMSEConsistency` for the student's classes; a module with that call signature; False = no teacher
+    pass and no consistency term (the EMA still runs).
+    consistency_weight, threshold_ramp: a float or an object with `.step(i)`; each step the engine writes
+    `weight_i` and `threshold_i = (0.75 + 0.25 * ramp_i) * ln(K)` into the device buffer `dyn` before anything reads it, outside
+    the autograd graph.  threshold_ramp None = 0, i.e. the schedule's strictest threshold `0.75 ln K` throughout.
+    uncertainty_passes: T extra teacher passes whose mean soft-max masks the consistency term; 0 = the plain Mean Teacher form.
+    noise_std, noise_clip: the teacher sees `image + clamp(N(0, noise_std^2), -noise_clip, noise_clip)`."""
+
+    _one_rank_why = " (the EMA and the teacher passes are not sharded yet)"
+
+    def __init__(self, model, teacher, supervised_loss, labeled_bs: int, ema_decay: float = 0.99, consistency=None,
+                 consistency_weight=0.1, uncertainty_passes: int = 0, threshold_ramp=None, noise_std: float = 0.1,
+                 noise_clip: float = 0.2, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
+                 start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
+                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("MeanTeacherEngine: ema_decay must lie in [0, 1]")
+        if uncertainty_passes < 0:
+            raise ValueError("MeanTeacherEngine: uncertainty_passes must not be negative")
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.teacher = teacher
+        self.supervised_loss = supervised_loss
+        self.ema_decay = float(ema_decay)
+        self.uncertainty_passes = int(uncertainty_passes)
+        self.consistency_weight, self.threshold_ramp = consistency_weight, threshold_ramp
+        self.noise_std, self.noise_clip = float(noise_std), float(noise_clip)
+        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
+        if consistency is None:
+            from losses.consistency_loss import SoftmaxMSEConsistency
+            consistency = SoftmaxMSEConsistency(self.num_classes - 1)
+        self.consistency = consistency or None
+        self._init_teacher()
+        self.last_supervised = self.last_consistency = self.last_kept = None
+
+    def _dyn_values(self):
+        r = 0.0 if self.threshold_ramp is None else _ramp_value(self.threshold_ramp, self.current_iter)
+        return _ramp_value(self.consistency_weight, self.current_iter), entropy_threshold(r, self.num_classes)
+
+    def _noisy(self, x: torch.Tensor) -> torch.Tensor:
+        if self.noise_std == 0.0:
+            return x
+        return x + torch.clamp(torch.randn_like(x) * self.noise_std, -self.noise_clip, self.noise_clip)
+
+    @torch.no_grad()
+    def _teacher_passes(self, unlabeled: torch.Tensor):
+        """(zt, pbar): the teacher's logits on one noisy copy, and the mean soft-max of `uncertainty_passes` further stochastic passes
+        (None without them).  Runs BEFORE the student's forward: `UNet.forward` clears the producer -> consumer hints that belong to
+        the backward of the latest forward."""
+        zt = self.teacher(self._noisy(unlabeled))
+        pbar = None
+        if self.uncertainty_passes > 0:
+            from inference.predictor import softmax_accum
+            pbar = torch.empty(zt.shape, device=zt.device, dtype=torch.float32)
+            for i in range(self.uncertainty_passes):
+                softmax_accum(self.teacher(self._noisy(unlabeled)), pbar, None, weight=1.0 / self.uncertainty_passes, first=i == 0)
+        return zt, pbar
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        lb = self.labeled_bs
+        consistent = self.consistency is not None and image.shape[0] > lb
+        if consistent:
+            self._write_dyn()
+            zt, pbar = self._teacher_passes(image[lb:])
+        output = self.model(image)
+        sup = self.supervised_loss(output[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        if not consistent:
+            return sup
+        loss = sup + self.consistency(output[lb:], zt, pbar, dyn=self.dyn)
+        self.last_consistency = getattr(self.consistency, "last_value", None)
+        self.last_kept = getattr(self.consistency, "last_kept", None)
+        return loss
 
 
 class URPCEngine(SemiEngine):
@@ -506,3 +522,116 @@ class VATEngine(SemiEngine):
         loss = sup + self.vat(out[lb:], z_clean, dyn=self.dyn)
         self.last_vat = getattr(self.vat, "last_value", None)
         return loss
+
+
+class BCPEngine(_EMATeacher, SemiEngine):
+    """student + EMA teacher + bidirectional copy-paste between labelled and unlabelled images + flat optimizer + poly LR.
+    `train_step` returns the loss TENSOR (no host sync); `last_inward`, `last_outward` (the two loss terms) and `last_mask` (uint8
+    [H, W]) are device by-products of the latest step.
+
+    A batch is as for the siblings, with B = 2 * labeled_bs and labeled_bs even (anything else raises `ValueError`).  With h =
+    labeled_bs / 2 the labelled halves are X_a, X_b with Y_a, Y_b and the unlabelled halves U_a, U_b.  A self-training step:
+
+        z_t  = teacher([U_a; U_b])                  ONE pass, no gradient, train mode, no input noise (as published); BEFORE the
+                                                    student's forward: `UNet.forward` clears the producer -> consumer hints
+        P    = argmax z_t                           (`softmax_accum`); with `pseudo_largest_component` the largest connected component
+                                                    of every foreground class and image is kept (`filter_components`)
+        M    = random_box_mask(H, W, mask_ratio)    one mask for the batch; 1 outside the box
+        in   = [M ? U_a : X_a ; M ? X_b : U_b]      two `ops.bcp_mix` calls into the halves of ONE network input: inward, outward
+        out  = model(in)                            ONE student forward
+        loss = CopyPasteLoss(out[:h], P_a, Y_a, M, u_weight, 1) + CopyPasteLoss(out[h:], Y_b, P_b, M, 1, u_weight)
+        backward, clip, step; then the EMA with `ema_alpha(ema_step, ema_decay)`
+
+    Where this departs from the published code: the mix is a selection, not `a * M + b * (1 - M)` (`ops.bcp_mix`); the two mixed
+    batches go through the network in one forward where the published code runs two -- per image the same with instance norm, while
+    with BATCH norm the statistics here span both mixes (two forwards of one network before a backward would also break the hint
+    mechanism); the pseudo-labels are cleaned by true connected components per class, where the published code keeps the largest
+    component of the foreground with a CPU library.  The Dice sums are per loss call (per mix), as published.
+
+    `pretrain=True` is the published pre-training: only the labelled images are used, the input is `M ? X_a : X_b` (h rows), the
+    loss `CopyPasteLoss(out, Y_a, Y_b, M, 1, 1)`, and the teacher is neither run nor updated.  `begin_self_training()` then makes the
+    teacher the student bit for bit and clears `pretrain`.
+    loss: None = `CopyPasteLoss` for the student's classes; a module with that call signature.
+    Eager steps, one rank, 2-D inputs, index labels."""
+
+    _one_rank_why = " (the EMA and the teacher pass are not sharded yet)"
+
+    def __init__(self, model, teacher, labeled_bs: int, u_weight: float = 0.5, mask_ratio: float = 2 / 3, ema_decay: float = 0.99,
+                 pseudo_largest_component: bool = True, pretrain: bool = False, loss=None, optimizer_name: str = "adam",
+                 optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250,
+                 lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError("BCPEngine: ema_decay must lie in [0, 1]")
+        if not 0.0 <= mask_ratio <= 1.0:
+            raise ValueError("BCPEngine: mask_ratio must lie in [0, 1]")
+        if labeled_bs < 2 or labeled_bs % 2:
+            raise ValueError(f"BCPEngine: labeled_bs={labeled_bs} must be even and at least 2 (the labelled images are mixed in two halves)")
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.teacher = teacher
+        self.ema_decay = float(ema_decay)
+        self.u_weight, self.mask_ratio = float(u_weight), float(mask_ratio)
+        self.pseudo_largest_component, self.pretrain = bool(pseudo_largest_component), bool(pretrain)
+        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
+        if loss is None:
+            from losses.copy_paste import CopyPasteLoss
+            loss = CopyPasteLoss(self.num_classes - 1)
+        self.loss = loss
+        self._init_teacher()
+        self.last_inward = self.last_outward = self.last_mask = None
+
+    def _stage(self, sampled_batch):
+        nimg, nlab = sampled_batch["image"].shape[0], sampled_batch["label"].shape[0]
+        if nimg != 2 * self.labeled_bs or nlab < self.labeled_bs:
+            raise ValueError(f"BCPEngine: {nimg} images / {nlab} label maps for labeled_bs={self.labeled_bs}; a batch holds labeled_bs "
+                             f"labelled images followed by as many unlabelled ones")
+        return super()._stage(sampled_batch)
+
+    @torch.no_grad()
+    def _pseudo_labels(self, unlabeled: torch.Tensor) -> torch.Tensor:
+        """int64 [n, H, W]: the arg-max of ONE teacher pass, cleaned to the largest component per foreground class and image."""
+        from inference.predictor import softmax_accum
+        zt = self.teacher(unlabeled)
+        pred = torch.empty((zt.shape[0],) + tuple(zt.shape[2:]), device=zt.device, dtype=torch.int64)
+        softmax_accum(zt, None, pred, first=True)
+        if self.pseudo_largest_component:
+            from inference.components import filter_components
+            pred = filter_components(pred, keep_largest=True, n_classes=self.num_classes)
+        return pred
+
+    def _mask(self, image: torch.Tensor) -> torch.Tensor:
+        from losses.copy_paste import random_box_mask
+        self.last_mask = random_box_mask(image.shape[2], image.shape[3], self.mask_ratio, device=image.device)
+        return self.last_mask
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        lb = self.labeled_bs
+        h = lb // 2
+        xa, xb, ya, yb = image[:h], image[h:lb], label[:h], label[h:lb]
+        if self.pretrain:
+            mask = self._mask(image)
+            loss = self.loss(self.model(ops.bcp_mix(xa, xb, mask)), ya, yb, mask, 1.0, 1.0)
+            self.last_inward, self.last_outward = loss.detach(), None
+            return loss
+        pseudo = self._pseudo_labels(image[lb:])
+        mask = self._mask(image)
+        net_in = torch.empty((lb,) + tuple(image.shape[1:]), device=image.device, dtype=torch.float32)
+        ops.bcp_mix(image[lb:lb + h], xa, mask, out=net_in[:h])  # inward: the labelled box inside an unlabelled image
+        ops.bcp_mix(xb, image[lb + h:], mask, out=net_in[h:])    # outward: the unlabelled box inside a labelled image
+        out = self.model(net_in)
+        inward = self.loss(out[:h], pseudo[:h], ya, mask, self.u_weight, 1.0)
+        outward = self.loss(out[h:], yb, pseudo[h:], mask, 1.0, self.u_weight)
+        self.last_inward, self.last_outward = inward.detach(), outward.detach()
+        return inward + outward
+
+    def _after_step(self) -> None:
+        if not self.pretrain:
+            super()._after_step()
+
+    def begin_self_training(self) -> None:
+        """The end of pre-training: the teacher becomes the student bit for bit (parameters and buffers), `pretrain` is cleared."""
+        with torch.no_grad():
+            self.teacher.load_state_dict(self.model.state_dict())  # copy_ into the flat-buffer views, and the buffers
+            self.teacher_flat.copy_(self.optimizer.flat_param)
+        ops.bump_param_epoch()
+        self.pretrain = False
