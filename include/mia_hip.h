@@ -732,6 +732,48 @@ int mia_bcp_loss_fwd(const float* logits, const void* label_a, const void* label
 int mia_bcp_loss_bwd(const float* logits, const void* label_a, const void* label_b, const unsigned char* mask, const float* coef,
                      const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
                      int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, int labels_u8, void* stream);
+/* Weak-to-strong consistency (csrc/w2s.hip; FixMatch: Sohn et al., NeurIPS 2020; UniMatch: Yang et al., CVPR 2023; CutMix-CPS; the
+ * reference has no such code; definition: losses/weak_strong.py). */
+#define MIA_W2S_MAX_CLASSES 8
+/* Pseudo-labels of the weak view: logits fp32 [nb][k1][hw] by (sn, sk, sp) like mia_cps_fwd, 1 <= k1 <= 8.  Per pixel
+ *   y = argmax_k z_k (on the fp32 logits, a tie to the LOWEST index),  keep = (max_k softmax(z)_k >= tau),  code = y | keep << 7
+ * tau = dyn_dev[1] read on the device (dyn_dev: DEVICE {weight, tau}; NULL = tau 0, every pixel kept; a NaN keeps nothing).  code:
+ * contiguous bytes [nb][hw]; kept[0] = sum keep as an exact int64.  An image's code does not depend on the rest of the batch.  Four
+ * pixels per thread under the rule of mia_cps_fwd (code 4-byte aligned), one otherwise.  slabs = blocks per image; workspace: nb * slabs
+ * 4-byte words. */
+int mia_w2s_labels(const float* logits, const float* dyn_dev, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int slabs,
+                   int* workspace, unsigned char* code, long long* kept, void* stream);
+/* CutMix of a batch with itself: out[n][c][p] = mask[n][p] != 0 ? x[src][c][p] : x[n][c][p] over contiguous fp32 x [nb][c][hw];
+ * perm: DEVICE int32[nb], src = (unsigned)perm[n] < nb ? perm[n] : n -- an entry outside the batch is never used as an index: the
+ * image is mixed with itself and the sticky verdict bad_perm[1] is set (bad_perm: DEVICE int32[2] laid out like bad_label; nothing
+ * on the device clears [1]).  mask, mask_sn, out, out_sn as mia_bcp_mix; out must not overlap x (checked from the address ranges).
+ * A selection: the bits of the chosen operand pass through.  16-byte accesses when hw % 4 == 0, x / out are 16-byte and mask 4-byte
+ * aligned and out_sn % 4 == 0; one element per thread otherwise; both give the same bits. */
+int mia_cutmix_perm(const float* x, const int* perm, const unsigned char* mask, float* out, int nb, int c, int64_t hw, int64_t mask_sn,
+                    int64_t out_sn, int* bad_perm, void* stream);
+/* The loss of the strong view: logits fp32 by (sn, sk, sp), 1 <= k1 <= 8; code: the byte map of mia_w2s_labels [nb][hw]; mask / perm as
+ * for mia_cutmix_perm, or either NULL for no mix (plain FixMatch).  For pixel (n, p): c = code[mask[n][p] ? src : n][p], y = c & 7,
+ * m = c >> 7 (a label >= k1 counts as not kept), q = softmax(z), N = nb * hw, sums over the whole call:
+ *   CE = (1/N) sum m (logsumexp(z) - z[y])              the denominator is always N; no kept pixel: 0
+ *   I_k = sum m q_k [y = k], Z_k = sum m q_k^2, Y_k = sum m [y = k] (exact integers)
+ *   D = (1/k1) sum_k (1 - (2 I_k + smooth) / (Z_k + Y_k + smooth))          no kept pixel: 0
+ *   L = weight (ce_weight CE + dice_weight D),  weight = dyn_dev[0] (NULL: 1)
+ * out[4] = {L, CE, D, weight}; counts[2] = {sum m over the mixed view, pixels whose mask byte is set (0 without a mix)}; coef[2 k1 +
+ * 1]: what the backward reads.  The backward recomputes the soft-max, re-reads code through mask / perm and writes dlogits =
+ * grad_out * dL/dz by (gsn, gsk, gsp) (grad_out: device pointer to one float or NULL for 1); a pixel with m = 0 gets exactly 0.  The
+ * perm guard and bad_perm are those of mia_cutmix_perm.  A thread owns the same four consecutive pixels on the 16-byte path (planar /
+ * channels-last logits, hw % 4 == 0, 16-byte aligned logits, 4-byte aligned code and mask; dlogits in the layout class of the logits)
+ * and on the scalar path, and every sum runs in one fixed order: the two paths give the same bits, and every result is bit-identical
+ * from run to run (no float atomics).  slabs = blocks per image of the forward; workspace: mia_w2s_loss_workspace 4-byte words.
+ * Limits: nb * hw < 2^31.  Every check happens before any launch; nothing synchronises with the host. */
+int mia_w2s_loss_workspace(int nb, int k1, int slabs); /* 4-byte words; < 0 for a bad shape */
+int mia_w2s_loss_fwd(const float* logits, const unsigned char* code, const unsigned char* mask, const int* perm, const float* dyn_dev,
+                     int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp, int64_t mask_sn, float smooth, float ce_weight,
+                     float dice_weight, int slabs, float* workspace, float* coef, float* out, long long* counts, int* bad_perm,
+                     void* stream);
+int mia_w2s_loss_bwd(const float* logits, const unsigned char* code, const unsigned char* mask, const int* perm, const float* coef,
+                     const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
+                     int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, void* stream);
 
 /* ------------------------------------------------------------------ virtual adversarial training (csrc/vat.hip) */
 /* KL distance between two fp32 logits tensors [nb][k1][hw], each addressed by its own (sn, sk, sp) / (tsn, tsk, tsp) element strides

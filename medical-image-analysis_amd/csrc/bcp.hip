@@ -59,17 +59,7 @@ __device__ __forceinline__ int bcp_class(unsigned lo, unsigned hi) {
   return (hi == 0u && lo < (unsigned)K1) ? (int)lo : -1;
 }
 
-// the mask bytes of the group's pixels as flags in bits 0, 8, 16, 24 ... kept as the bytes themselves: a pixel tests its byte != 0
-template <bool WIDE>
-__device__ __forceinline__ unsigned bcp_mask_bytes(const unsigned char* __restrict__ mk, int nlive) {
-  if (WIDE) return *reinterpret_cast<const unsigned*>(mk);
-  unsigned m = 0u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (i < nlive) m |= (unsigned)mk[i] << (8 * i);
-  return m;
-}
-
+// The mask bytes of the group's pixels (px4_bytes) are kept as the bytes themselves: a pixel tests its byte != 0.
 // the SELECTED label of each pixel of the group as a class index (-1: outside [0, K1), and every pixel past nlive)
 template <int K1, bool WIDE>
 __device__ __forceinline__ void bcp_labels(const long long* __restrict__ la, const long long* __restrict__ lb, unsigned mbytes,
@@ -113,24 +103,6 @@ __device__ __forceinline__ void bcp_labels(const unsigned char* __restrict__ la,
   }
 }
 
-// the logits of the group's four pixels from pixel p; the scalar path reads the live ones one by one and zeroes the rest
-template <int K1, int MODE>
-__device__ __forceinline__ void bcp_load(const float* __restrict__ img, int64_t p, int nlive, const LossGeom& g, float (&v)[4][K1]) {
-  if constexpr (MODE != CS_SCALAR) {
-    cs_load<K1, MODE>(img, p, g, v);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float t[1][K1];
-#pragma unroll
-      for (int k = 0; k < K1; ++k) t[0][k] = 0.f;
-      if (i < nlive) cs_load<K1, CS_SCALAR>(img, p + i, g, t);
-#pragma unroll
-      for (int k = 0; k < K1; ++k) v[i][k] = t[0][k];
-    }
-  }
-}
-
 // ---------------------------------------------------------------- forward
 template <int K1>
 struct BcpAcc {
@@ -150,7 +122,7 @@ __device__ __forceinline__ void bcp_fwd_pixel(const float (&v)[K1], int y, bool 
   double pmax = p[0];
 #pragma unroll
   for (int k = 1; k < K1; ++k) pmax = p[k] > pmax ? p[k] : pmax;
-  // logsumexp(v) - v[y] = -log(max_k p_k) + (max v - v[y]) (cps.hip: cps_term); v[y] as a sum of one value and K1 - 1 zeros
+  // logsumexp(v) - v[y] = -log(max_k p_k) + (max v - v[y]) (pixel_stream.h: cs_nll_term); v[y] as a sum of one value and K1 - 1 zeros
   float vy = 0.f;
 #pragma unroll
   for (int k = 0; k < K1; ++k) vy += (k == y) ? v[k] : 0.f;
@@ -170,14 +142,6 @@ __device__ __forceinline__ void bcp_fwd_pixel(const float (&v)[K1], int y, bool 
     a.cy[0][k] += in_a && t;
     a.cy[1][k] += in_b && t;
   }
-}
-
-// the wave's sum of v in double, parked by lane 0 as a (hi, lo) pair in the block's slots
-template <int NF, int NI>
-__device__ __forceinline__ void bcp_park(const LossBlockSums<NF, NI>& red, int slot, double v) {
-  float pr[2];
-  loss_split(wave_sum_d(v), pr);
-  if (red.l == 0) { red.f[red.w][slot] = pr[0]; red.f[red.w][slot + 1] = pr[1]; }
 }
 
 // block (image, slab of `per` pixels; per % 4 == 0).  Per region r the block's slice of the workspace holds wf_r [2 K1 + 1][2]: the
@@ -208,8 +172,8 @@ __global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restri
     const int nlive = r1 - p < 4 ? (int)(r1 - p) : 4;  // 4 on the 16-byte path (hw % 4 == 0)
     float v[4][K1];
     int y[4];
-    bcp_load<K1, MODE>(img, p, nlive, g, v);
-    const unsigned mb = bcp_mask_bytes<WIDE>(mk + p, nlive);
+    px4_load<K1, MODE>(img, p, nlive, g, v);
+    const unsigned mb = px4_bytes<WIDE>(mk + p, nlive);
     bcp_labels<K1, WIDE>(ia + p, ib + p, mb, nlive, y);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -224,12 +188,12 @@ __global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restri
   for (int r = 0; r < 2; ++r) {
 #pragma unroll
     for (int k = 0; k < K1; ++k) {
-      bcp_park(red, (r * NQ + k) * 2, acc.si[r][k]);
-      bcp_park(red, (r * NQ + K1 + k) * 2, acc.sz[r][k]);
+      cs_park(red, (r * NQ + k) * 2, acc.si[r][k]);
+      cs_park(red, (r * NQ + K1 + k) * 2, acc.sz[r][k]);
       const int c = wave_sum_i(acc.cy[r][k]);
       if (red.l == 0) red.i[red.w][r * NC + k] = c;
     }
-    bcp_park(red, (r * NQ + 2 * K1) * 2, acc.ce[r]);
+    cs_park(red, (r * NQ + 2 * K1) * 2, acc.ce[r]);
     const int c = wave_sum_i(acc.cn[r]);
     if (red.l == 0) red.i[red.w][r * NC + K1] = c;
   }
@@ -319,8 +283,8 @@ __global__ __launch_bounds__(256) void bcp_loss_bwd_kernel(const float* __restri
   for (int k = 0; k < NQ; ++k) { ca[k] = coef[k]; cb[k] = coef[NQ + k]; }
   float v[4][K1], d[4][K1];
   int y[4];
-  bcp_load<K1, MODE>(z + b * g.sn, p, nlive, g, v);
-  const unsigned mb = bcp_mask_bytes<WIDE>(mask + b * msn + p, nlive);
+  px4_load<K1, MODE>(z + b * g.sn, p, nlive, g, v);
+  const unsigned mb = px4_bytes<WIDE>(mask + b * msn + p, nlive);
   bcp_labels<K1, WIDE>(la + b * hw + p, lb + b * hw + p, mb, nlive, y);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

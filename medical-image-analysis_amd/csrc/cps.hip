@@ -24,53 +24,20 @@
 
 #define CPS_WORDS 7  // per block: (hi, lo) of the two sums, three counts
 
-// arg-max of the fp32 logits, the lowest index among equals; mx = the maximum.  Plain compares and selects over compile-time indices:
-// no register array is indexed at run time.
-template <int K1>
-__device__ __forceinline__ int cps_argmax(const float (&v)[K1], float& mx) {
-  int y = 0;
-  mx = v[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) {
-    const bool up = v[k] > mx;
-    mx = up ? v[k] : mx;
-    y = up ? k : y;
-  }
-  return y;
-}
-
-// logsumexp(v) - v[y] for the label y of the OTHER network: -log(max_k p_k) = log sum_k exp(v_k - max v) comes from the soft-max,
-// max v - v[y] is exact in double.  v[y] is picked as a sum of one value and K1 - 1 zeros (exact): a chain of selects between the
-// array's elements is turned into an indexed read of the array by the compiler, which then keeps the array in scratch memory.
-template <int K1>
-__device__ __forceinline__ double cps_term(const float (&v)[K1], int y, float mx, double pmax) {
-  float vy = 0.f;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) vy += (k == y) ? v[k] : 0.f;
-  return -log(pmax) + ((double)mx - (double)vy);
-}
-
-template <int K1>
-__device__ __forceinline__ double cps_max(const double (&p)[K1]) {
-  double r = p[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) r = p[k] > r ? p[k] : r;
-  return r;
-}
-
+// The arg-max (cs_argmax) and logsumexp(v) - v[y] for the label y of the OTHER network (cs_nll_term) are in pixel_stream.h.
 // one pixel of the forward: its code byte; the two terms and the three counts are added to the thread's running sums
 template <int K1>
 __device__ __forceinline__ unsigned cps_fwd_pixel(const float (&a)[K1], const float (&t)[K1], double tau, double& acc_a, double& acc_b,
                                                   int (&cnt)[3]) {
   float ma, mb;
-  const int ya = cps_argmax<K1>(a, ma), yb = cps_argmax<K1>(t, mb);
+  const int ya = cs_argmax<K1>(a, ma), yb = cs_argmax<K1>(t, mb);
   double pa[K1], pb[K1];
   cs_softmax<K1>(a, pa);
   cs_softmax<K1>(t, pb);
-  const double qa = cps_max<K1>(pa), qb = cps_max<K1>(pb);  // max_k p_k = 1 / sum_k exp(z_k - max)
+  const double qa = cs_max<K1>(pa), qb = cs_max<K1>(pb);  // max_k p_k = 1 / sum_k exp(z_k - max)
   const bool ca = qa >= tau, cb = qb >= tau;                // a NaN keeps nothing
-  if (cb) acc_a += cps_term<K1>(a, yb, ma, qa);
-  if (ca) acc_b += cps_term<K1>(t, ya, mb, qb);
+  if (cb) acc_a += cs_nll_term<K1>(a, yb, ma, qa);
+  if (ca) acc_b += cs_nll_term<K1>(t, ya, mb, qb);
   cnt[0] += ca;
   cnt[1] += cb;
   cnt[2] += ya == yb;

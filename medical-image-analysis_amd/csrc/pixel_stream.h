@@ -1,7 +1,8 @@
 // What the two-tensor streaming losses share (consistency.hip, cps.hip): the layout classes of a logits-shaped tensor, the loads and
 // stores of one thread's pixel group in each class, the per-pixel soft-max in double, and the host-side dispatch over
 // (class count, layout class of the first tensor, layout class of the second).  ONE definition of each piece, so that the files
-// cannot drift apart (loss_common.h, ds_common.h).  Their double-precision partial sums, which boundary.hip and urpc.hip use too, are in
+// cannot drift apart (loss_common.h, ds_common.h).  The losses over ONE logits tensor and per-pixel byte maps (bcp.hip, w2s.hip) add
+// the hard-label pieces (cs_argmax, cs_nll_term) and the four-pixel group (px4_*, cs_park).  Their double-precision partial sums, which boundary.hip and urpc.hip use too, are in
 // loss_common.h.
 #pragma once
 #include "loss_common.h"
@@ -29,6 +30,40 @@ __device__ __forceinline__ void cs_softmax(const float (&v)[K1], double (&s)[K1]
   const double inv = 1.0 / se;
 #pragma unroll
   for (int k = 0; k < K1; ++k) s[k] *= inv;
+}
+
+// arg-max of the fp32 logits, the lowest index among equals; mx = the maximum.  Plain compares and selects over compile-time indices:
+// no register array is indexed at run time.
+template <int K1>
+__device__ __forceinline__ int cs_argmax(const float (&v)[K1], float& mx) {
+  int y = 0;
+  mx = v[0];
+#pragma unroll
+  for (int k = 1; k < K1; ++k) {
+    const bool up = v[k] > mx;
+    mx = up ? v[k] : mx;
+    y = up ? k : y;
+  }
+  return y;
+}
+
+// logsumexp(v) - v[y] for a label y that need not be v's own arg-max: -log(max_k p_k) = log sum_k exp(v_k - max v) comes from the
+// soft-max, max v - v[y] is exact in double.  v[y] is picked as a sum of one value and K1 - 1 zeros (exact): a chain of selects between
+// the array's elements is turned into an indexed read of the array by the compiler, which then keeps the array in scratch memory.
+template <int K1>
+__device__ __forceinline__ double cs_nll_term(const float (&v)[K1], int y, float mx, double pmax) {
+  float vy = 0.f;
+#pragma unroll
+  for (int k = 0; k < K1; ++k) vy += (k == y) ? v[k] : 0.f;
+  return -log(pmax) + ((double)mx - (double)vy);
+}
+
+template <int K1>
+__device__ __forceinline__ double cs_max(const double (&p)[K1]) {
+  double r = p[0];
+#pragma unroll
+  for (int k = 1; k < K1; ++k) r = p[k] > r ? p[k] : r;
+  return r;
 }
 
 // the logits of PX consecutive pixels from pixel p of one image (`img` = the image's first element)
@@ -77,6 +112,45 @@ __device__ __forceinline__ void cs_store(float* __restrict__ img, int64_t p, con
 #pragma unroll
     for (int k = 0; k < K1; ++k) img[p * g.sp + k * g.sk] = v[0][k];
   }
+}
+
+// ---- a thread that owns FOUR consecutive pixels on the 16-byte path and on the scalar path alike (bcp.hip, w2s.hip)
+// four bytes of a per-pixel byte map (mask, code) from `mk`, byte i in bits 8 i ..: one 4-byte load, or the live ones one by one
+// and zeros for the rest
+template <bool WIDE>
+__device__ __forceinline__ unsigned px4_bytes(const unsigned char* __restrict__ mk, int nlive) {
+  if (WIDE) return *reinterpret_cast<const unsigned*>(mk);
+  unsigned m = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < nlive) m |= (unsigned)mk[i] << (8 * i);
+  return m;
+}
+
+// the logits of the group's four pixels from pixel p; the scalar path reads the live ones one by one and zeroes the rest
+template <int K1, int MODE>
+__device__ __forceinline__ void px4_load(const float* __restrict__ img, int64_t p, int nlive, const LossGeom& g, float (&v)[4][K1]) {
+  if constexpr (MODE != CS_SCALAR) {
+    cs_load<K1, MODE>(img, p, g, v);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float t[1][K1];
+#pragma unroll
+      for (int k = 0; k < K1; ++k) t[0][k] = 0.f;
+      if (i < nlive) cs_load<K1, CS_SCALAR>(img, p + i, g, t);
+#pragma unroll
+      for (int k = 0; k < K1; ++k) v[i][k] = t[0][k];
+    }
+  }
+}
+
+// the wave's sum of v in double, parked by lane 0 as a (hi, lo) pair in the block's slots
+template <int NF, int NI>
+__device__ __forceinline__ void cs_park(const LossBlockSums<NF, NI>& red, int slot, double v) {
+  float pr[2];
+  loss_split(wave_sum_d(v), pr);
+  if (red.l == 0) { red.f[red.w][slot] = pr[0]; red.f[red.w][slot + 1] = pr[1]; }
 }
 
 static inline bool cs_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }

@@ -2057,6 +2057,165 @@ class CopyPasteLossFn(torch.autograd.Function):
 CopyPasteLossFn.last_out = CopyPasteLossFn.last_counts = None
 
 
+# ------------------------------------------------------------------ weak-to-strong consistency (pseudo-label codes, CutMix, loss)
+W2S_MAX_CLASSES = 8
+_PERM_FLAGS = {}
+
+
+def _perm_flags(dev) -> torch.Tensor:
+    """Per-device int32[2], zeroed once, laid out like `_bad_flags`: [1] is the sticky verdict "a device `perm` held an entry outside
+    the batch" that the CutMix and weak-to-strong kernels raise and `check_perm()` reads and clears ([0] is unused: these kernels
+    have no working flag to fold)."""
+    key = (dev.type, dev.index)
+    t = _PERM_FLAGS.get(key)
+    if t is None:
+        t = torch.zeros(2, device=dev, dtype=torch.int32)
+        _PERM_FLAGS[key] = t
+    return t
+
+
+def check_perm() -> None:
+    """Raise if a `cutmix_perm` or `WeakToStrongFn` call on any device since the previous check met a DEVICE `perm` with an entry
+    outside [0, B) (host sync: call it where you already sync).  The kernels never use such an entry as an index: the image is paired
+    with itself, and the verdict is kept until this call reads and clears it.  A host `perm` is checked when it is given."""
+    for t in _PERM_FLAGS.values():
+        if int(t[1].item()) != 0:
+            t[1].zero_()
+            raise MiaError("CutMix: a device `perm` held an entry outside [0, B); that image was paired with itself")
+
+
+def _perm_arg(who: str, perm, b: int, dev) -> torch.Tensor:
+    """`perm` as a contiguous int32 [B] tensor on `dev`.  A device tensor is taken as it is (int32 [B], contiguous; the kernels guard
+    its entries).  A host sequence or a CPU tensor is validated here -- B integers in [0, B), not necessarily a permutation -- and
+    uploaded."""
+    if isinstance(perm, torch.Tensor) and perm.is_cuda:
+        if perm.dtype != torch.int32 or perm.ndim != 1 or perm.numel() != b or not perm.is_contiguous() or perm.device != dev:
+            raise MiaError(f"{who}: a device `perm` is a contiguous int32 [{b}] tensor on {dev}, got {perm.dtype} "
+                           f"{tuple(perm.shape)} on {perm.device}")
+        return perm
+    t = torch.as_tensor(perm)
+    if t.ndim != 1 or t.numel() != b or t.is_floating_point() or t.dtype == torch.bool:
+        raise MiaError(f"{who}: `perm` holds {b} integers, one per image; got {t.dtype} {tuple(t.shape)}")
+    t = t.to(torch.int64)
+    if b and (int(t.min()) < 0 or int(t.max()) >= b):
+        raise MiaError(f"{who}: `perm` entries must lie in [0, {b}); got {t.tolist()}")
+    return t.to(torch.int32).to(dev, non_blocking=True)
+
+
+def w2s_labels(zw: torch.Tensor, dyn: Optional[torch.Tensor] = None):
+    """(code, kept): the pseudo-labels of the weak view's logits `zw` [B, K, H, W] (include/mia_hip.h: mia_w2s_labels; csrc/w2s.hip).
+    `code` is uint8 [B, H, W] = argmax_k zw_k | keep << 7 with keep = (max_k softmax(zw)_k >= dyn[1]) -- ties to the lowest class, the
+    threshold read on the device (`dyn` None: 0, every pixel kept); `kept` is the 0-dim int64 count of kept pixels.  fp32, K <= 8, any
+    layout whose H and W collapse.  No gradient; an image's code does not depend on the rest of the batch (see `w2s_decode`)."""
+    _need_dev(zw, dyn)
+    if zw.ndim != 4:
+        raise NotImplementedError("the HIP weak-to-strong labels implement 2-D inputs [B, K, H, W]")
+    zw, st = _loss_logits(zw.detach())
+    b, k1, h, w = zw.shape
+    if not 1 <= k1 <= W2S_MAX_CLASSES:
+        raise MiaError(f"w2s_labels: {k1} classes not in [1, {W2S_MAX_CLASSES}] (pseudo_label_code of losses/weak_strong.py takes more)")
+    dyn = _dyn_arg("w2s_labels", dyn, 2, True)
+    hw = h * w
+    dev = zw.device
+    slabs = _two_logits_slabs(hw)
+    ws = torch.empty(max(b * slabs, 1), device=dev, dtype=torch.int32)
+    code = torch.empty((b, h, w), device=dev, dtype=torch.uint8)  # every byte is written by the kernel
+    kept = torch.empty(1, device=dev, dtype=torch.int64)
+    call("mia_w2s_labels", _p(zw), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(st), slabs, _p(ws), _p(code), _p(kept), _stream())
+    return code, kept[0]
+
+
+def w2s_decode(code: torch.Tensor):
+    """(y, keep) of a weak-to-strong code map: the label map (int64) and the confidence map (bool), in plain tensor ops on whatever
+    device `code` lives on -- for logging and tests, not the hot path."""
+    c = code.to(torch.int64)
+    return c & 7, ((c >> 7) & 1).bool()
+
+
+def cutmix_perm(x: torch.Tensor, perm, mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[n, c, p] = x[perm[n], c, p] where mask[n or 0, p] != 0, else x[n, c, p]: CutMix of a batch with a permutation of itself,
+    without the gathered copy `x[perm]` (include/mia_hip.h: mia_cutmix_perm; csrc/w2s.hip).  x: contiguous fp32 [B, C, H, W]; perm: B
+    integers (a host sequence or CPU tensor, validated here and uploaded; or a device int32 [B] tensor taken as it is -- see
+    `check_perm`); mask: uint8 [H, W] or [B, H, W]; out: None (a new tensor) or fp32 [B, C, H, W] whose images are dense, e.g. a batch
+    slice of a larger contiguous tensor, and which does not overlap `x`.  A SELECTION like `bcp_mix`: the bits of the chosen operand
+    pass through.  No gradient."""
+    _need_dev(x, mask, out)
+    if x.ndim != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise MiaError(f"cutmix_perm: a contiguous fp32 [B, C, H, W] batch expected, got {tuple(x.shape)} {x.dtype}")
+    b, c, h, w = x.shape
+    perm = _perm_arg("cutmix_perm", perm, b, x.device)
+    mask, msn = _bcp_mask("cutmix_perm", mask, b, h, w)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or \
+            out.stride()[1:] != x.stride()[1:] or (b > 1 and out.stride(0) < c * h * w):
+        raise MiaError("cutmix_perm: `out` is fp32 of the input's shape with dense images (a batch slice of a contiguous tensor)")
+    if x.numel() == 0:
+        return out
+    call("mia_cutmix_perm", _p(x.detach()), _p(perm), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn),
+         _c_i64(out.stride(0) if b > 1 else c * h * w), _p(_perm_flags(x.device)), _stream())
+    return out
+
+
+class WeakToStrongFn(torch.autograd.Function):
+    """`apply(logits, code, mask, perm, dyn, ce_weight, dice_weight, smooth)` -> the weak-to-strong loss of a strong view
+    (include/mia_hip.h: mia_w2s_loss_fwd; csrc/w2s.hip; the definition is the module text of losses/weak_strong.py): pixel (n, p) is
+    supervised by `code[perm[n], p]` where `mask[n or 0, p] != 0` and by `code[n, p]` elsewhere, wherever that code's confidence bit
+    is set.  `mask` or `perm` None: no mix.  One streaming forward pass and one streaming backward pass; only the logits get a
+    gradient.  fp32 logits [B, K, H, W], K <= 8, any layout whose H and W collapse; code uint8 [B, H, W] (`w2s_labels`); mask uint8
+    [H, W] or [B, H, W]; perm as for `cutmix_perm`; `dyn` None (weight 1) or the DEVICE fp32 {weight, threshold} -- the loss reads
+    the weight only.  By-products of the latest forward, on the device: `last_out` = {L, CE, D, weight} and `last_counts` (int64 [2]:
+    kept pixels of the mixed view, pixels taken from the partner)."""
+
+    @staticmethod
+    def forward(ctx, logits, code, mask, perm, dyn, ce_weight: float, dice_weight: float, smooth: float):
+        _need_dev(logits, code, mask, dyn)
+        if logits.ndim != 4:
+            raise NotImplementedError("the HIP weak-to-strong loss implements 2-D inputs [B, K, H, W]")
+        logits, st = _loss_logits(logits)
+        b, k1, h, w = logits.shape
+        if not 1 <= k1 <= W2S_MAX_CLASSES:
+            raise MiaError(f"weak-to-strong loss: {k1} classes not in [1, {W2S_MAX_CLASSES}] (the tensor-op form, fused=False, takes more)")
+        if code.dtype != torch.uint8 or tuple(code.shape) != (b, h, w):
+            raise MiaError(f"weak-to-strong loss: the code map is uint8 [{b}, {h}, {w}] (ops.w2s_labels), got {code.dtype} "
+                           f"{tuple(code.shape)}")
+        code = code.contiguous()
+        dev = logits.device
+        msn = 0
+        if mask is None or perm is None:
+            mask = perm = None
+        else:
+            mask, msn = _bcp_mask("weak-to-strong loss", mask, b, h, w)
+            perm = _perm_arg("weak-to-strong loss", perm, b, dev)
+        dyn = _dyn_arg("weak-to-strong loss", dyn, 2, True)
+        hw = h * w
+        slabs = _two_logits_slabs(hw)
+        words = max(lib().mia_w2s_loss_workspace(b, k1, slabs), 0)  # < 0: a bad shape, reported by the call below
+        ncoef = 2 * k1 + 1
+        buf = torch.empty(words + ncoef + 4, device=dev, dtype=torch.float32)  # workspace | coef | out[4]: every word written
+        ws, coef, out = buf[:words], buf[words:words + ncoef], buf[words + ncoef:]
+        counts = torch.empty(2, device=dev, dtype=torch.int64)
+        call("mia_w2s_loss_fwd", _p(logits), _p(code), _p(mask), _p(perm), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(st), _c_i64(msn),
+             _c_float(smooth), _c_float(ce_weight), _c_float(dice_weight), slabs, _p(ws), _p(coef), _p(out), _p(counts),
+             _p(_perm_flags(dev)), _stream())
+        ctx.save_for_backward(logits, code, coef)
+        ctx.mask, ctx.perm, ctx.st, ctx.msn = mask, perm, st, msn
+        WeakToStrongFn.last_out, WeakToStrongFn.last_counts = out, counts
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, code, coef = ctx.saved_tensors
+        b, k1, h, w = logits.shape
+        dl, gst, g = _loss_bwd_begin(logits, gout)
+        call("mia_w2s_loss_bwd", _p(logits), _p(code), _p(ctx.mask), _p(ctx.perm), _p(coef), _p(g), _p(dl), b, _c_i64(h * w), k1,
+             *_strides_i64(ctx.st), *_strides_i64(gst), _c_i64(ctx.msn), _stream())
+        return dl, None, None, None, None, None, None, None
+
+
+WeakToStrongFn.last_out = WeakToStrongFn.last_counts = None
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 

@@ -26,7 +26,8 @@ convention, same device-resident schedule buffer `dyn`; it runs eagerly on one r
 `CPSEngine` is cross pseudo supervision (CPS: Chen et al., CVPR 2021), the two-network row of those tables: two networks of different
 initialisation, both trained, each on the supervised loss plus cross-entropy on the other's hard pseudo-labels
 (`losses.cross_pseudo.CrossPseudoSupervisionLoss`, csrc/cps.hip).  One `backward()` feeds two `FlatOptimizer`s.  Same batch
-convention and `dyn = {weight, confidence threshold}`; eager, one rank, 2-D inputs.  Out of scope: CutMix-CPS, Dice on pseudo-labels.
+convention and `dyn = {weight, confidence threshold}`; eager, one rank, 2-D inputs.  `cutmix=True` is the CutMix form, on the
+weak-to-strong kernels described below.  Out of scope: Dice on pseudo-labels.
 
 `VATEngine` is virtual adversarial training (VAT: Miyato et al., TPAMI 2018), the one semi-supervised method the reference itself ships
 (`losses/adv_loss.py`): one network, no teacher.  The unlabelled images are pushed `eps` along the direction that changes the
@@ -38,8 +39,22 @@ clean image.  Same batch convention, `dyn = {weight, eps}`; eager, one rank, 2-D
 images: a box of a labelled image is pasted into an unlabelled one and the other way round (`ops.bcp_mix`), and every pixel of a mixed
 image is supervised by the ground truth or by the EMA teacher's pseudo-label, whichever image it came from
 (`losses.copy_paste.CopyPasteLoss`, csrc/bcp.hip).  It shares the teacher machinery (`_EMATeacher`) with `MeanTeacherEngine`.  Eager,
-one rank, 2-D inputs, index labels.  Out of scope: CutMix-CPS (the mix kernel and the mask generator are what it would need), 3-D
-volumes, per-image masks in the engine (the kernels take them).
+one rank, 2-D inputs, index labels.  Out of scope: 3-D volumes, per-image masks in the engine (the kernels take them).
+
+`FixMatchEngine` is weak-to-strong consistency (FixMatch: Sohn et al., NeurIPS 2020; with two strong views the dual-stream perturbation
+of UniMatch: Yang et al., CVPR 2023): one network and no teacher.  The network predicts on the unlabelled images as they come (the
+weak view); its confident arg-max labels (`ops.w2s_labels`) supervise the SAME network on strongly augmented views of those images
+that are CutMix-ed with a permutation of themselves (`ops.cutmix_perm`), where a pixel under a box takes the pseudo-label of the image
+it came from (`losses.weak_strong.WeakToStrongLoss`, csrc/w2s.hip).  Same batch convention, `dyn = {u_weight, confidence threshold}`;
+eager, one rank, 2-D inputs.  As in FixMatch's published code the labelled and the strong rows share one forward, and with batch norm
+its statistics.  Where it departs from the published code: the weak view, which shares that forward there, has a gradient-free pass
+of its own here that leaves the running statistics alone (`ops.no_bn_tracking`; two forwards of one network before a backward would
+break the hint mechanism, so the weak pass comes first); the images of the batch ARE the weak view (the geometric augmentation
+happens upstream); the CutMix partner is a permutation of the unlabelled half of the SAME batch where UniMatch draws a second
+unlabelled batch from the loader; the mix is a selection, not a blend; the box aspect is drawn from the part of the range that fits
+instead of redrawn until it does; the CE denominator is always the pixel count, where UniMatch divides by the kept pixels.  Out of
+scope: UniMatch's feature-perturbation stream (Dropout2d on the skips between encoder and decoder), graph capture, more than one
+rank, 3-D.
 """
 from __future__ import annotations
 
@@ -373,14 +388,35 @@ class CPSEngine(SemiEngine):
     network B's carry the suffix `_b`.
     cps_weight, confidence_threshold: a float or an object with `.step(i)`; each step the engine writes `weight_i` and `tau_i` into the
     device buffer `dyn` before anything reads it, outside the autograd graph.  tau = 0 (the default) is the published CPS; tau > 0
-    lets a network learn only from labels whose source gives them a soft-max of at least tau."""
+    lets a network learn only from labels whose source gives them a soft-max of at least tau.
+
+    `cutmix=True` is the CutMix form of the paper: the pseudo-labels come from the CLEAN unlabelled images and the
+    networks are trained on a CutMix of them.  With U = image[lb:], per step
+
+        za = model_a(U);  zb = model_b(U)           no gradient, batch-norm running statistics untouched, BEFORE the training forwards
+        code_a = ops.w2s_labels(za, dyn)[0];  code_b = ops.w2s_labels(zb, dyn)[0]
+        mask = box_masks(random_cutmix_boxes(nu, H, W, cutmix_prob, cutmix_size, cutmix_ratio));  perm = torch.randperm(nu)
+        net_in = [image[:lb]; ops.cutmix_perm(U, perm, mask)]             ONE input for both networks
+        out_a = model_a(net_in);  out_b = model_b(net_in)
+        loss  = sup + w2s(out_a[lb:], code_b, mask, perm, dyn=dyn) + w2s(out_b[lb:], code_a, mask, perm, dyn=dyn)
+
+    with `w2s = WeakToStrongLoss(K - 1, ce_weight=1, dice_weight=0)` (csrc/w2s.hip): a pixel under a box is supervised by the OTHER
+    network's label of the image it came from.  `last_cps` is then the unweighted sum of the two CE terms, `last_confident` the two
+    networks' confident pixels on the clean images, `last_agree` None; `last_mask`, `last_perm`, `last_net_in` and `last_codes`
+    (the two code maps) are further by-products.  The unlabelled images mix among themselves (the paper mixes two unlabelled batches); `cps_on_labeled` does not
+    combine with it.  With `cutmix=False`, the default, not one launch differs from the plain form above."""
 
     def __init__(self, model_a, model_b, supervised_loss, labeled_bs: int, cps_weight=0.1, confidence_threshold=0.0,
                  cps_on_labeled: bool = False, optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None,
                  start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250, lr_interval: int = 1,
-                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+                 lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None, cutmix: bool = False,
+                 cutmix_prob: float = 1.0, cutmix_size=(0.02, 0.4), cutmix_ratio=(0.3, 1 / 0.3)):
         if model_a is model_b:
             raise ValueError("CPSEngine needs two networks: model_a and model_b are the same object")
+        if cutmix and cps_on_labeled:
+            raise ValueError("CPSEngine: cutmix=True mixes the unlabelled images only; cps_on_labeled does not combine with it")
+        if not 0.0 <= cutmix_prob <= 1.0:
+            raise ValueError("CPSEngine: cutmix_prob must lie in [0, 1]")
         ka, kb = (int(m.decoder.seg_output.weight.shape[0]) for m in (model_a, model_b))
         if ka != kb:
             raise ValueError(f"CPSEngine: the networks predict {ka} and {kb} classes")
@@ -396,7 +432,13 @@ class CPSEngine(SemiEngine):
         self.num_classes = ka  # K: background included
         from losses.cross_pseudo import CrossPseudoSupervisionLoss
         self.cps = CrossPseudoSupervisionLoss(self.num_classes - 1)
+        self.cutmix = bool(cutmix)
+        self.cutmix_prob, self.cutmix_size, self.cutmix_ratio = float(cutmix_prob), tuple(cutmix_size), tuple(cutmix_ratio)
+        if self.cutmix:
+            from losses.weak_strong import WeakToStrongLoss
+            self.w2s = WeakToStrongLoss(self.num_classes - 1, ce_weight=1.0, dice_weight=0.0)
         self.last_supervised = self.last_cps = self.last_agree = self.last_confident = None
+        self.last_mask = self.last_perm = self.last_net_in = self.last_codes = None
 
     def _nets(self):
         return (self.model, self.model_b)
@@ -407,8 +449,38 @@ class CPSEngine(SemiEngine):
     def _dyn_values(self):
         return _ramp_value(self.cps_weight, self.current_iter), _ramp_value(self.confidence_threshold, self.current_iter)
 
+    def _cutmix_loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        from losses.weak_strong import box_masks, random_cutmix_boxes
+        lb = self.labeled_bs
+        nu = image.shape[0] - lb
+        self._write_dyn()
+        image = image.contiguous()
+        unlabeled = image[lb:]
+        with torch.no_grad(), ops.no_bn_tracking():
+            code_a, kept_a = ops.w2s_labels(self.model(unlabeled), self.dyn)
+            code_b, kept_b = ops.w2s_labels(self.model_b(unlabeled), self.dyn)
+        h, w = image.shape[2:]
+        mask = box_masks(random_cutmix_boxes(nu, h, w, self.cutmix_prob, self.cutmix_size, self.cutmix_ratio), h, w, image.device)
+        perm = torch.randperm(nu).to(torch.int32).to(image.device, non_blocking=True)
+        net_in = torch.empty_like(image)
+        net_in[:lb] = image[:lb]
+        ops.cutmix_perm(unlabeled, perm, mask, out=net_in[lb:])
+        out_a = self.model(net_in)
+        out_b = self.model_b(net_in)
+        sup = self.supervised_loss(out_a[:lb], label[:lb]) + self.supervised_loss(out_b[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        loss = sup + self.w2s(out_a[lb:], code_b, mask, perm, dyn=self.dyn)
+        ce_a = self.w2s.last_ce
+        loss = loss + self.w2s(out_b[lb:], code_a, mask, perm, dyn=self.dyn)
+        self.last_cps = ce_a + self.w2s.last_ce
+        self.last_agree, self.last_confident = None, torch.stack([kept_a, kept_b])
+        self.last_mask, self.last_perm, self.last_net_in, self.last_codes = mask, perm, net_in, (code_a, code_b)
+        return loss
+
     def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
         lb = self.labeled_bs
+        if self.cutmix and image.shape[0] > lb:
+            return self._cutmix_loss(image, label)
         out_a = self.model(image)
         out_b = self.model_b(image)
         sup = self.supervised_loss(out_a[:lb], label[:lb]) + self.supervised_loss(out_b[:lb], label[:lb])
@@ -635,3 +707,117 @@ class BCPEngine(_EMATeacher, SemiEngine):
             self.teacher_flat.copy_(self.optimizer.flat_param)
         ops.bump_param_epoch()
         self.pretrain = False
+
+
+class FixMatchEngine(SemiEngine):
+    """one network + supervised loss on the labelled images + weak-to-strong consistency on the unlabelled ones + flat optimizer +
+    poly LR.  `train_step` returns the loss TENSOR (no host sync).  Device by-products of the latest step: `last_supervised`;
+    `last_unsup` (the unsupervised term as it enters the loss: the mean over the views of the WEIGHTED `WeakToStrongLoss`);
+    `last_kept` (int64: confident pixels of the weak view); `last_code` (uint8 [nu, H, W], the weak view's code map); `last_masks`
+    (per view uint8 [nu, H, W], 1 inside the CutMix box), `last_perms` (per view int32 [nu]) and `last_net_in` (the ONE input of the
+    student's forward).  With lb = labeled_bs, U = image[lb:], nu = len(U), V = strong_views (1: FixMatch, 2: UniMatch's dual-stream
+    perturbation), one step is
+
+        zw = model(U)                               no gradient, batch-norm running statistics untouched (`ops.no_bn_tracking`);
+                                                    BEFORE the student's forward: `UNet.forward` clears the producer -> consumer hints
+        code, kept = ops.w2s_labels(zw, dyn)        arg-max and [confidence >= dyn[1]] per pixel, one byte
+        for v in range(V):
+            S_v    = strong_transform(U)            an intensity-only `BatchedAugment` (brightness, contrast, gamma, blur, noise; its
+                                                    own draws per view); geometry untouched, so pixel p of S_v is pixel p of U;
+                                                    None = identity
+            mask_v = box_masks(random_cutmix_boxes(nu, H, W, cutmix_prob, cutmix_size, cutmix_ratio));  perm_v = torch.randperm(nu)
+            net_in[lb + v nu : lb + (v + 1) nu] = ops.cutmix_perm(S_v, perm_v, mask_v)        straight into the rows of ONE input
+        net_in[:lb] = image[:lb]
+        out  = model(net_in)                        ONE student forward
+        loss = supervised_loss(out[:lb], label[:lb]) + (1/V) sum_v w2s(out[rows of v], code, mask_v, perm_v, dyn=dyn)
+
+    The images of the batch are the weak view: the geometric augmentation happens upstream in `BatchedAugment`, as for every engine
+    here.  Boxes and permutations are drawn on the host (`torch.manual_seed` reproduces a run; nothing syncs).  With batch norm the
+    statistics of the one forward span the labelled and the strong rows, as in the published code.  With no unlabelled image or
+    `loss=False` the engine forwards `image[:lb]` only and returns the supervised loss.
+    u_weight, confidence_threshold: a float or an object with `.step(i)`; each step the engine writes `weight_i` and `tau_i` into the
+    device buffer `dyn` before anything reads it, outside the autograd graph.
+    strong_transform: called as `strong_transform(U, zero labels)` -- a `BatchedAugment` with `inplace=False` and no resize, or any
+    callable of that signature; the result is a dict with "image" or the image tensor itself, and must have U's shape.
+    loss: None = `WeakToStrongLoss(K - 1, ce_weight, dice_weight)`; a module with that call signature; False = no unsupervised term.
+    The checkpoint is the base engine's: there is no extra state."""
+
+    def __init__(self, model, supervised_loss, labeled_bs: int, u_weight=1.0, confidence_threshold=0.95, strong_views: int = 1,
+                 strong_transform=None, cutmix_prob: float = 0.5, cutmix_size=(0.02, 0.4), cutmix_ratio=(0.3, 1 / 0.3), loss=None,
+                 ce_weight: float = 1.0, dice_weight: float = 0.0, optimizer_name: str = "adam",
+                 optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250,
+                 lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+        if strong_views < 1:
+            raise ValueError("FixMatchEngine: strong_views must be at least 1")
+        if not 0.0 <= cutmix_prob <= 1.0:
+            raise ValueError("FixMatchEngine: cutmix_prob must lie in [0, 1]")
+        if getattr(strong_transform, "inplace", False):
+            raise ValueError("FixMatchEngine: strong_transform must not work in place (the unlabelled images are the weak view, and "
+                             "every strong view starts from them)")
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.supervised_loss = supervised_loss
+        self.u_weight, self.confidence_threshold = u_weight, confidence_threshold
+        self.strong_views, self.strong_transform = int(strong_views), strong_transform
+        self.cutmix_prob, self.cutmix_size, self.cutmix_ratio = float(cutmix_prob), tuple(cutmix_size), tuple(cutmix_ratio)
+        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
+        if loss is None:
+            from losses.weak_strong import WeakToStrongLoss
+            loss = WeakToStrongLoss(self.num_classes - 1, ce_weight, dice_weight)
+        self.w2s = loss or None
+        self.last_supervised = self.last_unsup = self.last_kept = self.last_code = None
+        self.last_masks = self.last_perms = self.last_net_in = None
+
+    def _dyn_values(self):
+        return _ramp_value(self.u_weight, self.current_iter), _ramp_value(self.confidence_threshold, self.current_iter)
+
+    def _strong(self, unlabeled: torch.Tensor) -> torch.Tensor:
+        if self.strong_transform is None:
+            return unlabeled
+        out = self.strong_transform(unlabeled, torch.zeros((unlabeled.shape[0],) + tuple(unlabeled.shape[2:]),
+                                                           device=unlabeled.device, dtype=torch.int64))
+        strong = out["image"] if isinstance(out, dict) else out
+        if strong.shape != unlabeled.shape:
+            raise ValueError(f"FixMatchEngine: strong_transform changed the shape {tuple(unlabeled.shape)} -> {tuple(strong.shape)}; "
+                             f"the strong view must keep the geometry of the weak one")
+        return strong.to(torch.float32).contiguous()
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        from losses.weak_strong import box_masks, random_cutmix_boxes
+        lb = self.labeled_bs
+        nu = image.shape[0] - lb
+        if self.w2s is None or nu <= 0:
+            sup = self.supervised_loss(self.model(image[:lb]), label[:lb])
+            self.last_supervised = sup.detach()
+            return sup
+        self._write_dyn()
+        image = image.contiguous()
+        unlabeled = image[lb:]
+        with torch.no_grad(), ops.no_bn_tracking():
+            zw = self.model(unlabeled)
+        code, self.last_kept = ops.w2s_labels(zw, self.dyn)
+        views = self.strong_views
+        h, w = image.shape[2:]
+        dev = image.device
+        net_in = torch.empty((lb + views * nu,) + tuple(image.shape[1:]), device=dev, dtype=torch.float32)
+        masks, perms = [], []
+        for v in range(views):
+            strong = self._strong(unlabeled)
+            mask = box_masks(random_cutmix_boxes(nu, h, w, self.cutmix_prob, self.cutmix_size, self.cutmix_ratio), h, w, dev)
+            perm = torch.randperm(nu).to(torch.int32).to(dev, non_blocking=True)  # a permutation by construction: taken as it is
+            ops.cutmix_perm(strong, perm, mask, out=net_in[lb + v * nu:lb + (v + 1) * nu])
+            masks.append(mask)
+            perms.append(perm)
+        net_in[:lb] = image[:lb]
+        out = self.model(net_in)
+        sup = self.supervised_loss(out[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        unsup = None
+        for v in range(views):
+            term = self.w2s(out[lb + v * nu:lb + (v + 1) * nu], code, masks[v], perms[v], dyn=self.dyn)
+            unsup = term if unsup is None else unsup + term
+        if views > 1:
+            unsup = unsup / views
+        self.last_unsup, self.last_code = unsup.detach(), code
+        self.last_masks, self.last_perms, self.last_net_in = masks, perms, net_in
+        return sup + unsup

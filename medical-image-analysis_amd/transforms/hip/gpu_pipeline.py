@@ -39,6 +39,20 @@ def al_train_transforms(dataset: str = "fugc", elastic: bool = False) -> Compose
     ])
 
 
+def strong_intensity_transforms(p: float = 0.8) -> ComposeTransform:
+    """The intensity stages of `al_train_transforms` alone, each firing with probability `p`: the strong view of weak-to-strong
+    consistency (`training.semi.FixMatchEngine(strong_transform=BatchedAugment(strong_intensity_transforms()))`).  No geometric
+    stage and no resampling: pixel p of the strong view is pixel p of the weak one, which is what lets the weak view's
+    pseudo-labels supervise it (build-side addition: the reference has no such pipeline)."""
+    return ComposeTransform([
+        RandomTransform(RandomBrightness(brightness=(0.75, 1.25)), p=p),
+        RandomTransform(RandomContrast(contrast=(0.75, 1.25)), p=p),
+        RandomTransform(RandomGamma(gamma=(0.7, 1.5)), p=p),
+        RandomTransform(RandomGaussianBlur(sigma=(0.5, 1.0)), p=p),
+        RandomTransform(RandomGaussianNoise(sigma=(0, 0.1)), p=p),
+    ])
+
+
 class BatchedAugment:
     """images [B,C,H0,W0] f32 in [0,1], labels [B,H0,W0] or [B,1,H0,W0] int64 on the GPU ->
     {"image": [B,C,S,S] f32, "label": [B,S,S] int64} ready for ``train_step``."""
