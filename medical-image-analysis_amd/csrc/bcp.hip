@@ -6,27 +6,21 @@
 // chosen operand pass through as they are (NaN payloads and -0.0 included), and the operand not chosen is never looked at.
 //
 // Loss: logits z [nb][k1][hw] fp32 by (sn, sk, sp), label maps ya, yb [nb][hw] (int64 or uint8), mask byte m per pixel; region A is
-// m != 0 and reads ya, region B is m == 0 and reads yb.  With p = softmax(z), for each region r over ALL images and pixels of the call
-//   I_rk = sum m_r p_k [y_r = k]   Z_rk = sum m_r p_k^2   Y_rk = sum m_r [y_r = k]   N_r = sum m_r        (Y, N exact integers)
-//   D_r = (1/K) sum_k (1 - (2 I_rk + s) / (Z_rk + Y_rk + s))       every class counts, background included
-//   C_r = sum m_r (logsumexp(z) - z[y_r]) / (N_r + 1e-16)           an empty region: D_r = C_r = 0
+// m != 0 and reads ya, region B is m == 0 and reads yb.  The hard-label Dice + CE core (hard_loss.h) with R = 2 regions over ALL images
+// and pixels of the call, every class counting, background included:
+//   wd_r = wc_r = w_r / 2,  cden_r = N_r + 1e-16            an empty region: D_r = C_r = 0
 //   L = wa (D_A + C_A) / 2 + wb (D_B + C_B) / 2
-//   out = {L, D_A, C_A, D_B, C_B};  counts = {N_A, N_B}
-//   dL/dz_j = (w_r/2) [ (p_j - [j = y_r]) / (N_r + 1e-16) + p_j (g_rj - sum_k g_rk p_k) ],  g_rk = al_rk [y_r = k] + be_rk p_k,
-//   al_rk = -2 / (K den_rk), be_rk = 2 (2 I_rk + s) / (K den_rk^2), den_rk = Z_rk + Y_rk + s
-//   coef [2][2 k1 + 1] = per region {(w_r/2) al_rk}, {(w_r/2) be_rk}, (w_r/2) / (N_r + 1e-16): what the backward reads
-//   bcp_loss_fwd_kernel   block (image, slab of pixels): ONE streaming pass over logits, mask byte and the two label maps; the soft-max
-//                         in double per pixel (cs_softmax); a pixel adds into its own region's sums by predication; per-block partials
-//                         through LossBlockSums as (hi, lo) float pairs (loss_split) and ints
+//   out = {L, D_A, C_A, D_B, C_B};  counts = {N_A, N_B};  coef [2][2 k1 + 1]: what the backward reads
+//   bcp_loss_fwd_kernel   block (image, slab of pixels): ONE streaming pass over logits, mask byte and the two label maps
 //   bcp_finalize_kernel   one block: the partials in a fixed order in double / int64 (loss_totals, once per region) -> out, counts, coef
-//   bcp_loss_bwd_kernel   one streaming pass, a thread per pixel group: recomputes the soft-max, picks the region's coefficients by
-//                         the mask byte, writes dlogits by its own strides
+//   bcp_loss_bwd_kernel   one streaming pass, a thread per pixel group: picks the region's coefficients by the mask byte, writes
+//                         dlogits by its own strides
 // A pixel reads ONLY its own region's label: the other map may hold anything there.  A selected label outside [0, k1) follows the
 // protocol of the other losses (loss_bad_label_verdict): NaN results and the sticky per-device verdict.
 // A thread owns the SAME four consecutive pixels on the 16-byte path (planar / channels-last logits, hw % 4 == 0, aligned pointers
 // and strides) and on the scalar path, and every sum runs in the same order on both, so the two paths give the same bits.  No float
 // atomics: bit-identical from run to run.  Nothing synchronises with the host.
-#include "pixel_stream.h"
+#include "hard_loss.h"
 
 // ---------------------------------------------------------------- mix
 // WIDE: a thread owns four consecutive pixels of one (image, channel) plane: two 16-byte loads, one 4-byte mask load, one 16-byte store
@@ -104,48 +98,7 @@ __device__ __forceinline__ void bcp_labels(const unsigned char* __restrict__ la,
 }
 
 // ---------------------------------------------------------------- forward
-template <int K1>
-struct BcpAcc {
-  double si[2][K1], sz[2][K1], ce[2];
-  int cy[2][K1], cn[2];
-};
-
-// one pixel: `in_a` / `in_b` say which region it adds to (neither: a pixel past the end of the image).  Every index into the
-// accumulators is a constant; the region is chosen by predication, so no register array is indexed at run time.
-template <int K1>
-__device__ __forceinline__ void bcp_fwd_pixel(const float (&v)[K1], int y, bool in_a, bool in_b, BcpAcc<K1>& a) {
-  float mx = v[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) mx = fmaxf(mx, v[k]);
-  double p[K1];
-  cs_softmax<K1>(v, p);
-  double pmax = p[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) pmax = p[k] > pmax ? p[k] : pmax;
-  // logsumexp(v) - v[y] = -log(max_k p_k) + (max v - v[y]) (pixel_stream.h: cs_nll_term); v[y] as a sum of one value and K1 - 1 zeros
-  float vy = 0.f;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) vy += (k == y) ? v[k] : 0.f;
-  const double term = y >= 0 ? -log(pmax) + ((double)mx - (double)vy) : 0.0;
-  a.ce[0] += in_a ? term : 0.0;
-  a.ce[1] += in_b ? term : 0.0;
-  a.cn[0] += in_a;
-  a.cn[1] += in_b;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) {
-    const bool t = y == k;
-    const double q = p[k] * p[k];
-    a.si[0][k] += (in_a && t) ? p[k] : 0.0;
-    a.si[1][k] += (in_b && t) ? p[k] : 0.0;
-    a.sz[0][k] += in_a ? q : 0.0;
-    a.sz[1][k] += in_b ? q : 0.0;
-    a.cy[0][k] += in_a && t;
-    a.cy[1][k] += in_b && t;
-  }
-}
-
-// block (image, slab of `per` pixels; per % 4 == 0).  Per region r the block's slice of the workspace holds wf_r [2 K1 + 1][2]: the
-// (hi, lo) pairs of I_rk, Z_rk, CE_r, and wn_r [K1 + 1]: Y_rk, N_r.
+// block (image, slab of `per` pixels; per % 4 == 0); the workspace is laid out by hl_park
 template <int K1, int MODE, typename LT>
 __global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restrict__ z, const LT* __restrict__ la,
                                                            const LT* __restrict__ lb, const unsigned char* __restrict__ mask,
@@ -159,14 +112,8 @@ __global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restri
   const unsigned char* mk = mask + b * msn;
   const LT* ia = la + (int64_t)b * hw;
   const LT* ib = lb + (int64_t)b * hw;
-  BcpAcc<K1> acc;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    acc.ce[r] = 0.0;
-    acc.cn[r] = 0;
-#pragma unroll
-    for (int k = 0; k < K1; ++k) { acc.si[r][k] = 0.0; acc.sz[r][k] = 0.0; acc.cy[r][k] = 0; }
-  }
+  HlAcc<K1, 2> acc;
+  acc.zero();
   bool bad = false;
   for (int64_t p = r0 + (int64_t)threadIdx.x * 4; p < r1; p += 256 * 4) {
     const int nlive = r1 - p < 4 ? (int)(r1 - p) : 4;  // 4 on the 16-byte path (hw % 4 == 0)
@@ -179,34 +126,12 @@ __global__ __launch_bounds__(256) void bcp_loss_fwd_kernel(const float* __restri
     for (int i = 0; i < 4; ++i) {
       const bool live = i < nlive, m = ((mb >> (8 * i)) & 0xffu) != 0u;
       bad |= live && y[i] < 0;
-      bcp_fwd_pixel<K1>(v[i], y[i], live && m, live && !m, acc);
+      const bool in[2] = {live && m, live && !m};
+      hl_fwd_pixel<K1, 2>(v[i], y[i], in, acc);
     }
   }
   if (bad) *bad_label = 1;
-  auto red = loss_block_sums<2 * 2 * NQ, 2 * NC>();
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-#pragma unroll
-    for (int k = 0; k < K1; ++k) {
-      cs_park(red, (r * NQ + k) * 2, acc.si[r][k]);
-      cs_park(red, (r * NQ + K1 + k) * 2, acc.sz[r][k]);
-      const int c = wave_sum_i(acc.cy[r][k]);
-      if (red.l == 0) red.i[red.w][r * NC + k] = c;
-    }
-    cs_park(red, (r * NQ + 2 * K1) * 2, acc.ce[r]);
-    const int c = wave_sum_i(acc.cn[r]);
-    if (red.l == 0) red.i[red.w][r * NC + K1] = c;
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < 4 * NQ) {  // region t / (2 NQ), word t % (2 NQ) of this block's pairs
-    const int r = t / (2 * NQ), j = t % (2 * NQ);
-    ws[((size_t)r * nparts + blockIdx.x) * (2 * NQ) + j] = red.sum_f(t);
-  } else if (t >= 128 && t < 128 + 2 * NC) {
-    const int r = (t - 128) / NC, j = (t - 128) % NC;
-    int* wn = reinterpret_cast<int*>(ws + (size_t)2 * nparts * (2 * NQ));
-    wn[((size_t)r * nparts + blockIdx.x) * NC + j] = red.sum_i(t - 128);
-  }
+  hl_park<K1, 2, 0>(acc, nullptr, ws, nparts);
 }
 
 // one block of 256 threads: out[5], counts[2], coef[2][2 K1 + 1]
@@ -227,24 +152,8 @@ __global__ __launch_bounds__(256) void bcp_finalize_kernel(const float* __restri
     __syncthreads();
   }
   if (t < 2) {  // one thread per region
-    const int r = t;
-    const double n = (double)tn[r][K1], s = (double)smooth, hw_ = 0.5 * (double)(r ? wb : wa);
-    double d = 0.0, c = 0.0;
-    if (tn[r][K1] > 0) {
-      for (int k = 0; k < K1; ++k) {
-        const double num = 2.0 * tf[r][k] + s, den = tf[r][K1 + k] + (double)tn[r][k] + s;
-        d += 1.0 - num / den;
-        cf[r * NQ + k] = (float)(hw_ * (-2.0 / ((double)K1 * den)));
-        cf[r * NQ + K1 + k] = (float)(hw_ * (2.0 * num / ((double)K1 * den * den)));
-      }
-      d /= (double)K1;
-      c = tf[r][2 * K1] / (n + 1e-16);
-      cf[r * NQ + 2 * K1] = (float)(hw_ / (n + 1e-16));
-    } else {  // an empty region: no term, and no pixel reads these
-      for (int k = 0; k < NQ; ++k) cf[r * NQ + k] = 0.f;
-    }
-    term[r][0] = d;
-    term[r][1] = c;
+    const double hw_ = 0.5 * (double)(t ? wb : wa);
+    hl_region<K1>(tf[t], tn[t], (double)smooth, hw_, hw_, (double)tn[t][K1] + 1e-16, term[t][0], term[t][1], cf + t * NQ);
   }
   __syncthreads();
   if (t == 0) {
@@ -289,17 +198,13 @@ __global__ __launch_bounds__(256) void bcp_loss_bwd_kernel(const float* __restri
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const bool m = ((mb >> (8 * i)) & 0xffu) != 0u;
-    double pr[K1], gk[K1], dot = 0.0;
-    cs_softmax<K1>(v[i], pr);
+    float cf[NQ];  // the pixel's region
 #pragma unroll
-    for (int k = 0; k < K1; ++k) {
-      const double al = (double)(m ? ca[k] : cb[k]), be = (double)(m ? ca[K1 + k] : cb[K1 + k]);
-      gk[k] = (y[i] == k ? al : 0.0) + be * pr[k];
-      dot += gk[k] * pr[k];
-    }
-    const double cec = (double)(m ? ca[2 * K1] : cb[2 * K1]);
+    for (int k = 0; k < NQ; ++k) cf[k] = m ? ca[k] : cb[k];
+    float t[K1];  // not d[i] itself: handed the row, the channels-last instantiations keep up to 24 more registers (occupancy 6 -> 4)
+    hl_bwd_pixel<K1>(v[i], y[i], true, cf, go, t);
 #pragma unroll
-    for (int k = 0; k < K1; ++k) d[i][k] = (float)(go * (cec * (pr[k] - (y[i] == k ? 1.0 : 0.0)) + pr[k] * (gk[k] - dot)));
+    for (int k = 0; k < K1; ++k) d[i][k] = t[k];
   }
   float* dst = dz + b * gd.sn;
   if constexpr (WIDE) {
@@ -344,21 +249,17 @@ static void bcp_launch_bwd(hipStream_t st, const float* z, const void* la, const
                        static_cast<const long long*>(lb), mask, coef, gout, dz, hw, msn, groups, total, g, gd);
 }
 
-template <int K1, int MODE>
+template <int K1, int MODE>  // MODE unused: the shape CS_DISPATCH1 calls
 static void bcp_launch_finalize(hipStream_t st, const float* ws, int nparts, float smooth, float wa, float wb, float* out,
                                 long long* counts, float* coef, int* bad_label) {
   hipLaunchKernelGGL(bcp_finalize_kernel<K1>, dim3(1), dim3(256), 0, st, ws, nparts, smooth, wa, wb, out, counts, coef, bad_label);
 }
 
-static inline bool bcp_al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
-// the 16-byte path: the logits' class, four pixels per unit in every map (labels as 16-byte units of int64 or 4-byte words of uint8,
-// the mask as 4-byte words)
+// the 16-byte path: px4_mode with the mask, and four labels per unit (16-byte units of int64 or 4-byte words of uint8)
 static int bcp_mode(const float* z, const LossGeom& g, int k1, int64_t hw, const void* la, const void* lb, bool u8,
                     const unsigned char* mask) {
-  const int sm = cs_mode(z, g, k1);
-  if (sm == CS_SCALAR || hw % 4 != 0 || !bcp_al4(mask)) return CS_SCALAR;
-  if (u8 ? !(bcp_al4(la) && bcp_al4(lb)) : !(cs_al16(la) && cs_al16(lb))) return CS_SCALAR;
-  return sm;
+  if (u8 ? !(cs_al4(la) && cs_al4(lb)) : !(cs_al16(la) && cs_al16(lb))) return CS_SCALAR;
+  return px4_mode(z, g, k1, hw, mask, nullptr);
 }
 
 static size_t bcp_words_per_block(int k1) { return (size_t)2 * ((2 * k1 + 1) * 2 + k1 + 1); }
@@ -366,23 +267,16 @@ static size_t bcp_words_per_block(int k1) { return (size_t)2 * ((2 * k1 + 1) * 2
 extern "C" int mia_bcp_mix(const float* fg, const float* bg, const unsigned char* mask, float* out, int nb, int c, int64_t hw,
                            int64_t mask_sn, int64_t out_sn, void* stream) {
   MIA_CHECK_ARG(fg && bg && mask && out, "mia_bcp_mix: null pointer");
-  MIA_CHECK_ARG(nb > 0 && c > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)c * hw <= 0x7fffffff &&
-                    ceil_div64((int64_t)nb * c * hw, 256) <= 0x7fffffff,
-                "mia_bcp_mix: bad shape nb=%d c=%d hw=%lld", nb, c, (long long)hw);
-  MIA_CHECK_ARG((mask_sn == 0 || mask_sn == hw) && out_sn >= (int64_t)c * hw, "mia_bcp_mix: bad strides mask_sn=%lld out_sn=%lld",
-                (long long)mask_sn, (long long)out_sn);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t chw = (int64_t)c * hw;
-  const bool wide = hw % 4 == 0 && out_sn % 4 == 0 && cs_al16(fg) && cs_al16(bg) && cs_al16(out) && bcp_al4(mask);
-  const int64_t total = (int64_t)nb * (wide ? chw / 4 : chw);
-  const dim3 grid((unsigned)ceil_div64(total, 256)), blk(256);
   const unsigned* f = reinterpret_cast<const unsigned*>(fg);
   const unsigned* b = reinterpret_cast<const unsigned*>(bg);
   unsigned* o = reinterpret_cast<unsigned*>(out);
-  if (wide) hipLaunchKernelGGL(bcp_mix_kernel<true>, grid, blk, 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
-  else hipLaunchKernelGGL(bcp_mix_kernel<false>, grid, blk, 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return px4_mix_launch("mia_bcp_mix", fg, bg, mask, out, nb, c, hw, mask_sn, out_sn,
+                        [&](bool wide, dim3 grid, int64_t chw, int64_t total) -> int {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (wide) hipLaunchKernelGGL(bcp_mix_kernel<true>, grid, dim3(256), 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
+    else hipLaunchKernelGGL(bcp_mix_kernel<false>, grid, dim3(256), 0, st, f, b, mask, o, hw, chw, mask_sn, out_sn, total);
+    return MIA_OK;
+  });
 }
 
 extern "C" int mia_bcp_loss_workspace(int nb, int k1, int slabs) {
@@ -396,13 +290,9 @@ extern "C" int mia_bcp_loss_fwd(const float* logits, const void* label_a, const 
                                 long long* counts, int* bad_label, void* stream) {
   MIA_CHECK_ARG(logits && label_a && label_b && mask && workspace && coef && out && counts && bad_label,
                 "mia_bcp_loss_fwd: null pointer");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_bcp_loss_fwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
-  MIA_CHECK_ARG(nb > 0 && hw > 0 && slabs > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff &&
-                    (int64_t)nb * slabs * (int64_t)bcp_words_per_block(k1) <= 0x7fffffff,
-                "mia_bcp_loss_fwd: bad shape nb=%d hw=%lld slabs=%d", nb, (long long)hw, slabs);
-  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && (mask_sn == 0 || mask_sn == hw), "mia_bcp_loss_fwd: bad strides");
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const LossGeom g{sn, sk, sp};
+  if (const int e = hl_check("mia_bcp_loss_fwd", nb, hw, k1, slabs, bcp_words_per_block(k1), g, nullptr, mask_sn)) return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   const bool u8 = labels_u8 != 0;
   const int sm = bcp_mode(logits, g, k1, hw, label_a, label_b, u8, mask);
   CS_DISPATCH1(bcp_launch_fwd, st, logits, label_a, label_b, u8, mask, nb, hw, mask_sn, g, slabs, workspace, bad_label);
@@ -416,13 +306,9 @@ extern "C" int mia_bcp_loss_bwd(const float* logits, const void* label_a, const 
                                 int64_t sk, int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, int labels_u8,
                                 void* stream) {
   MIA_CHECK_ARG(logits && label_a && label_b && mask && coef && dlogits, "mia_bcp_loss_bwd: null pointer");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_bcp_loss_bwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
-  MIA_CHECK_ARG(nb > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff, "mia_bcp_loss_bwd: bad shape nb=%d hw=%lld",
-                nb, (long long)hw);
-  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && gsn >= 0 && gsk >= 0 && gsp >= 0 && (mask_sn == 0 || mask_sn == hw),
-                "mia_bcp_loss_bwd: bad strides");
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const LossGeom g{sn, sk, sp}, gd{gsn, gsk, gsp};
+  if (const int e = hl_check("mia_bcp_loss_bwd", nb, hw, k1, 0, 0, g, &gd, mask_sn)) return e;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   const bool u8 = labels_u8 != 0;
   int sm = bcp_mode(logits, g, k1, hw, label_a, label_b, u8, mask);
   if (cs_mode(dlogits, gd, k1) != sm) sm = CS_SCALAR;  // the gradient in the layout class of its logits, or one pixel at a time

@@ -1,9 +1,13 @@
-// What the two-tensor streaming losses share (consistency.hip, cps.hip): the layout classes of a logits-shaped tensor, the loads and
-// stores of one thread's pixel group in each class, the per-pixel soft-max in double, and the host-side dispatch over
-// (class count, layout class of the first tensor, layout class of the second).  ONE definition of each piece, so that the files
-// cannot drift apart (loss_common.h, ds_common.h).  The losses over ONE logits tensor and per-pixel byte maps (bcp.hip, w2s.hip) add
-// the hard-label pieces (cs_argmax, cs_nll_term) and the four-pixel group (px4_*, cs_park).  Their double-precision partial sums, which boundary.hip and urpc.hip use too, are in
-// loss_common.h.
+// What the streaming losses over logits-shaped tensors share.  ONE definition of each piece, so that the files cannot drift apart
+// (loss_common.h, ds_common.h).
+//   consistency.hip, cps.hip, bcp.hip, w2s.hip   the layout classes of a logits-shaped tensor (cs_mode), the loads and stores of one
+//                                 thread's pixel group in each class (cs_load, cs_store), the per-pixel soft-max in double (cs_softmax)
+//   consistency.hip, cps.hip      the dispatch over (class count, layout class of the first tensor, of the second): CS_DISPATCH
+//   cps.hip, w2s.hip, hard_loss.h the hard-label pieces: cs_argmax, cs_nll_term, cs_max
+//   bcp.hip, w2s.hip              a thread that owns FOUR consecutive pixels on every path (px4_*, cs_park), the dispatch over (class
+//                                 count, layout class): CS_DISPATCH1, and the launch of a mix under a mask (px4_mix_launch); their
+//                                 Dice + CE core is hard_loss.h
+// The double-precision partial sums, which boundary.hip and urpc.hip use too, are in loss_common.h.
 #pragma once
 #include "loss_common.h"
 
@@ -153,6 +157,7 @@ __device__ __forceinline__ void cs_park(const LossBlockSums<NF, NI>& red, int sl
   if (red.l == 0) { red.f[red.w][slot] = pr[0]; red.f[red.w][slot + 1] = pr[1]; }
 }
 
+static inline bool cs_al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
 static inline bool cs_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 // the four-pixel layout class of a logits-shaped tensor whose base and image stride are 16-byte aligned, else CS_SCALAR
 static int cs_mode(const void* base, const LossGeom& g, int k1) {
@@ -160,6 +165,31 @@ static int cs_mode(const void* base, const LossGeom& g, int k1) {
   if (g.sp == 1 && g.sk % 4 == 0) return CS_PLANAR4;
   if (g.sk == 1 && g.sp == k1) return CS_CLAST4;
   return CS_SCALAR;
+}
+// the same for a thread that owns four pixels of the logits and of up to two byte maps (mask, code; a null one passes): the maps are
+// read as 4-byte words
+static int px4_mode(const void* z, const LossGeom& g, int k1, int64_t hw, const void* m0, const void* m1) {
+  return hw % 4 == 0 && cs_al4(m0) && cs_al4(m1) ? cs_mode(z, g, k1) : CS_SCALAR;
+}
+
+// The body of mia_bcp_mix and mia_cutmix_perm after their pointer checks: out [nb][c][hw] fp32 (image stride out_sn) takes each
+// element from a or from b by the mask byte of its pixel.  WIDE (four pixels per thread: 16-byte loads and stores, the mask as 4-byte
+// words) when every operand allows it.  `launch(wide, grid, chw, total)` starts the caller's kernel and returns MIA_OK, or its own
+// error.
+template <typename F>
+static int px4_mix_launch(const char* who, const void* a, const void* b, const unsigned char* mask, const void* out, int nb, int c,
+                          int64_t hw, int64_t mask_sn, int64_t out_sn, F&& launch) {
+  MIA_CHECK_ARG(nb > 0 && c > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)c * hw <= 0x7fffffff &&
+                    ceil_div64((int64_t)nb * c * hw, 256) <= 0x7fffffff,
+                "%s: bad shape nb=%d c=%d hw=%lld", who, nb, c, (long long)hw);
+  MIA_CHECK_ARG((mask_sn == 0 || mask_sn == hw) && out_sn >= (int64_t)c * hw, "%s: bad strides mask_sn=%lld out_sn=%lld", who,
+                (long long)mask_sn, (long long)out_sn);
+  const int64_t chw = (int64_t)c * hw;
+  const bool wide = hw % 4 == 0 && out_sn % 4 == 0 && cs_al16(a) && cs_al16(b) && cs_al16(out) && cs_al4(mask);
+  const int64_t total = (int64_t)nb * (wide ? chw / 4 : chw);
+  if (const int e = launch(wide, dim3((unsigned)ceil_div64(total, 256)), chw, total)) return e;
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
 }
 
 // FN<K1, SM, TM>(args...) for the run-time (k1, student mode, teacher mode); the modes are both CS_SCALAR or both four-pixel classes
@@ -183,7 +213,7 @@ static int cs_mode(const void* base, const LossGeom& g, int k1) {
     default: CS_MODES(FN, 8, __VA_ARGS__); break;       \
   }
 
-// The same for a loss over ONE logits tensor (bcp.hip): FN<K1, SM>(args...) for the run-time (k1, sm)
+// The same for a loss over ONE logits tensor (bcp.hip, w2s.hip): FN<K1, SM>(args...) for the run-time (k1, sm)
 #define CS_MODES1(FN, K, ...)                                          \
   do {                                                                 \
     if (sm == CS_SCALAR) FN<K, CS_SCALAR>(__VA_ARGS__);                \

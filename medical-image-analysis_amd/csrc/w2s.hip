@@ -14,29 +14,26 @@
 // to fold [0] into [1] the kernels here raise [1] themselves, and nothing re-arms it but the host's check).
 //
 // Loss: strong logits zs [nb][k1][hw] fp32 by (sn, sk, sp), the code map above, mask / perm as for the mix (both NULL: no mix).  For
-// pixel (n, p): c = code[mask[n][p] ? src(n) : n][p], y = c & 7, m = c >> 7, q = softmax(zs), N = nb * hw, sums over the WHOLE call
-//   CE  = (1/N) sum m (logsumexp(zs) - zs[y])                     the denominator is always N (cps.hip); no kept pixel: 0
-//   I_k = sum m q_k [y = k]   Z_k = sum m q_k^2   Y_k = sum m [y = k]              (Y exact integers)
-//   D   = (1/K) sum_k (1 - (2 I_k + s) / (Z_k + Y_k + s))         no kept pixel: 0
-//   L   = w (ce_w CE + dice_w D),  w = dyn[0] (dyn NULL: 1)
-//   out = {L, CE, D, w};  counts = {sum m over the mixed view, pixels whose mask byte is set (0 without a mix)}
-//   dL/dzs_j = m [ cec (q_j - [j = y]) + q_j (g_j - sum_k g_k q_k) ],  g_k = al_k [y = k] + be_k q_k,
-//   cec = w ce_w / N, al_k = -2 w dice_w / (K den_k), be_k = 2 w dice_w (2 I_k + s) / (K den_k^2), den_k = Z_k + Y_k + s
-//   coef [2 k1 + 1] = {al_k}, {be_k}, cec: what the backward reads; a pixel with m = 0 gets exactly 0.0f
+// pixel (n, p): c = code[mask[n][p] ? src(n) : n][p], y = c & 7, kept = c >> 7.  The hard-label Dice + CE core (hard_loss.h) with ONE
+// region, the kept pixels of the WHOLE call:
+//   wd = w dice_w,  wc = w ce_w,  w = dyn[0] (dyn NULL: 1),  cden = nb * hw: always every pixel (cps.hip); no kept pixel: CE = D = 0
+//   L = w (ce_w CE + dice_w D)
+//   out = {L, CE, D, w};  counts = {kept pixels of the mixed view, pixels whose mask byte is set (0 without a mix)}
+//   coef [2 k1 + 1]: what the backward reads; a pixel that is not kept gets exactly 0.0f
 //   w2s_labels_kernel     block (image, slab of pixels): one streaming pass over zw; soft-max in double per pixel (cs_softmax); writes
 //                         `code` (one 4-byte store per four pixels on the wide path) and the block's count
 //   w2s_count_kernel      one block: the counts in a fixed order in int64
 //   w2s_cutmix_kernel     a thread per four elements (16-byte path) or per element
 //   w2s_loss_fwd_kernel   block (image, slab of pixels): ONE streaming pass over zs, the mask byte and the one or two code bytes of a
-//                         pixel; per-block partials through LossBlockSums as (hi, lo) float pairs (loss_split) and ints
+//                         pixel
 //   w2s_finalize_kernel   one block: the partials in a fixed order in double / int64 (loss_totals) -> out, counts, coef
-//   w2s_loss_bwd_kernel   one streaming pass, a thread per pixel group: recomputes the soft-max, re-reads `code` through mask / perm
-//                         (so both directions agree on every pixel), writes dzs by its own strides
+//   w2s_loss_bwd_kernel   one streaming pass, a thread per pixel group: re-reads `code` through mask / perm (so both directions agree
+//                         on every pixel), writes dzs by its own strides
 // A code byte whose label is not below k1 (a map made for more classes) counts as not kept.  A thread owns the SAME four consecutive
 // pixels on the 16-byte path (planar / channels-last logits, hw % 4 == 0, aligned pointers and strides) and on the scalar path, and
 // every sum runs in the same order on both, so the two paths give the same bits.  No float atomics: bit-identical from run to run; an
 // image's code does not depend on the rest of the batch; nothing synchronises with the host.
-#include "pixel_stream.h"
+#include "hard_loss.h"
 
 // ---------------------------------------------------------------- labels
 template <int K1>
@@ -150,37 +147,8 @@ __device__ __forceinline__ bool w2s_decode(unsigned c, int& y) {
 }
 
 // ---------------------------------------------------------------- forward
-template <int K1>
-struct W2sAcc {
-  double si[K1], sz[K1], ce;
-  int cy[K1], cn;
-};
-
-// one pixel: it adds to the sums when `live` (not past the end of the image) and kept.  Every index into the accumulators is a
-// constant; the choice is made by predication, so no register array is indexed at run time.
-template <int K1>
-__device__ __forceinline__ void w2s_fwd_pixel(const float (&v)[K1], unsigned c, bool live, W2sAcc<K1>& a) {
-  int y;
-  const bool m = w2s_decode<K1>(c, y) && live;
-  float mx = v[0];
-#pragma unroll
-  for (int k = 1; k < K1; ++k) mx = fmaxf(mx, v[k]);
-  double p[K1];
-  cs_softmax<K1>(v, p);
-  const double term = cs_nll_term<K1>(v, y, mx, cs_max<K1>(p));
-  a.ce += m ? term : 0.0;
-  a.cn += m;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) {
-    const bool t = m && y == k;
-    a.si[k] += t ? p[k] : 0.0;
-    a.sz[k] += m ? p[k] * p[k] : 0.0;
-    a.cy[k] += t;
-  }
-}
-
-// block (image, slab of `per` pixels; per % 4 == 0).  The block's slice of the workspace holds wf [2 K1 + 1][2]: the (hi, lo) pairs of
-// I_k, Z_k, the CE sum, and wn [K1 + 2]: Y_k, the kept pixels, the pixels whose mask byte is set.
+// block (image, slab of `per` pixels; per % 4 == 0); the workspace is laid out by hl_park, the block's third count is the pixels whose
+// mask byte is set
 template <int K1, int MODE>
 __global__ __launch_bounds__(256) void w2s_loss_fwd_kernel(const float* __restrict__ z, const unsigned char* __restrict__ code,
                                                            const unsigned char* __restrict__ mask, const int* __restrict__ perm,
@@ -200,11 +168,8 @@ __global__ __launch_bounds__(256) void w2s_loss_fwd_kernel(const float* __restri
   const unsigned char* mk = mask ? mask + b * msn : nullptr;
   const unsigned char* cown = code + (int64_t)b * hw;
   const unsigned char* coth = code + (int64_t)src * hw;
-  W2sAcc<K1> acc;
-  acc.ce = 0.0;
-  acc.cn = 0;
-#pragma unroll
-  for (int k = 0; k < K1; ++k) { acc.si[k] = 0.0; acc.sz[k] = 0.0; acc.cy[k] = 0; }
+  HlAcc<K1, 1> acc;
+  acc.zero();
   int pasted = 0;
   for (int64_t p = r0 + (int64_t)threadIdx.x * 4; p < r1; p += 256 * 4) {
     const int nlive = r1 - p < 4 ? (int)(r1 - p) : 4;  // 4 on the 16-byte path (hw % 4 == 0)
@@ -215,28 +180,13 @@ __global__ __launch_bounds__(256) void w2s_loss_fwd_kernel(const float* __restri
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       pasted += ((mb >> (8 * i)) & 0xffu) != 0u;  // the bytes past nlive are zero
-      w2s_fwd_pixel<K1>(v[i], (cd >> (8 * i)) & 0xffu, i < nlive, acc);
+      int y;
+      const bool in[1] = {w2s_decode<K1>((cd >> (8 * i)) & 0xffu, y) && i < nlive};
+      hl_fwd_pixel<K1, 1>(v[i], y, in, acc);
     }
   }
-  auto red = loss_block_sums<2 * NQ, NC>();
-#pragma unroll
-  for (int k = 0; k < K1; ++k) {
-    cs_park(red, k * 2, acc.si[k]);
-    cs_park(red, (K1 + k) * 2, acc.sz[k]);
-    const int c = wave_sum_i(acc.cy[k]);
-    if (red.l == 0) red.i[red.w][k] = c;
-  }
-  cs_park(red, 2 * K1 * 2, acc.ce);
-  const int cn = wave_sum_i(acc.cn), cp = wave_sum_i(pasted);
-  if (red.l == 0) { red.i[red.w][K1] = cn; red.i[red.w][K1 + 1] = cp; }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < 2 * NQ) {
-    ws[(size_t)blockIdx.x * (2 * NQ) + t] = red.sum_f(t);
-  } else if (t >= 128 && t < 128 + NC) {
-    int* wn = reinterpret_cast<int*>(ws + (size_t)nparts * (2 * NQ));
-    wn[(size_t)blockIdx.x * NC + (t - 128)] = red.sum_i(t - 128);
-  }
+  const int extra[1] = {pasted};
+  hl_park<K1, 1, 1>(acc, extra, ws, nparts);
 }
 
 // one block of 256 threads: out[4], counts[2], coef[2 K1 + 1]
@@ -252,21 +202,10 @@ __global__ __launch_bounds__(256) void w2s_finalize_kernel(const float* __restri
   const int t = threadIdx.x;
   if (t == 0) {
     const float wt = dyn ? dyn[0] : 1.f;
-    const double s = (double)smooth, wd = (double)wt * (double)dice_w;
-    double d = 0.0;
-    if (tot.n[K1] > 0) {
-      for (int k = 0; k < K1; ++k) {
-        const double num = 2.0 * tot.f[k] + s, den = tot.f[K1 + k] + (double)tot.n[k] + s;
-        d += 1.0 - num / den;
-        cf[k] = (float)(wd * (-2.0 / ((double)K1 * den)));
-        cf[K1 + k] = (float)(wd * (2.0 * num / ((double)K1 * den * den)));
-      }
-      d /= (double)K1;
-    } else {  // no kept pixel: no term, and no pixel reads these
-      for (int k = 0; k < 2 * K1; ++k) cf[k] = 0.f;
-    }
-    const double ce = tot.f[2 * K1] / n_all;
-    cf[2 * K1] = (float)((double)wt * (double)ce_w / n_all);
+    const double wc = (double)wt * (double)ce_w;
+    double d, ce;
+    hl_region<K1>(tot.f, tot.n, (double)smooth, (double)wt * (double)dice_w, wc, n_all, d, ce, cf);
+    cf[2 * K1] = (float)(wc / n_all);  // the CE denominator never vanishes: this one is written with no kept pixel too
     res[0] = (float)((double)wt * ((double)ce_w * ce + (double)dice_w * d));
     res[1] = (float)ce;
     res[2] = (float)d;
@@ -308,21 +247,11 @@ __global__ __launch_bounds__(256) void w2s_loss_bwd_kernel(const float* __restri
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int y;
-    if (w2s_decode<K1>((cd >> (8 * i)) & 0xffu, y)) {
-      double pr[K1], gk[K1], dot = 0.0;
-      cs_softmax<K1>(v[i], pr);
+    const bool kept = w2s_decode<K1>((cd >> (8 * i)) & 0xffu, y);
+    float t[K1];  // not d[i] itself (bcp.hip): handed the row, <4, planar> gets a store-data site at 3 wait states behind a store
+    hl_bwd_pixel<K1>(v[i], y, kept, cf, go, t);
 #pragma unroll
-      for (int k = 0; k < K1; ++k) {
-        gk[k] = (y == k ? (double)cf[k] : 0.0) + (double)cf[K1 + k] * pr[k];
-        dot += gk[k] * pr[k];
-      }
-      const double cec = (double)cf[2 * K1];
-#pragma unroll
-      for (int k = 0; k < K1; ++k) d[i][k] = (float)(go * (cec * (pr[k] - (y == k ? 1.0 : 0.0)) + pr[k] * (gk[k] - dot)));
-    } else {
-#pragma unroll
-      for (int k = 0; k < K1; ++k) d[i][k] = 0.f;  // a dropped pixel: exactly zero
-    }
+    for (int k = 0; k < K1; ++k) d[i][k] = t[k];
   }
   float* dst = dz + b * gd.sn;
   if constexpr (WIDE) {
@@ -357,7 +286,7 @@ static void w2s_launch_fwd(hipStream_t st, const float* z, const unsigned char* 
                      g, slabs, per, ws, nb * slabs, bad_perm);
 }
 
-template <int K1, int MODE>
+template <int K1, int MODE>  // MODE unused: the shape CS_DISPATCH1 calls
 static void w2s_launch_finalize(hipStream_t st, const float* ws, int nparts, double n_all, const float* dyn, float smooth, float ce_w,
                                 float dice_w, float* out, long long* counts, float* coef) {
   hipLaunchKernelGGL(w2s_finalize_kernel<K1>, dim3(1), dim3(256), 0, st, ws, nparts, n_all, dyn, smooth, ce_w, dice_w, out, counts,
@@ -373,14 +302,6 @@ static void w2s_launch_bwd(hipStream_t st, const float* z, const unsigned char* 
                      coef, gout, dz, nb, hw, msn, groups, total, g, gd);
 }
 
-static inline bool w2s_al4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; }
-// the 16-byte path of the loss: the logits' class, four pixels per 4-byte word in the code map and in the mask
-static int w2s_mode(const float* z, const LossGeom& g, int k1, int64_t hw, const unsigned char* code, const unsigned char* mask) {
-  const int sm = cs_mode(z, g, k1);
-  if (sm == CS_SCALAR || hw % 4 != 0 || !w2s_al4(code) || !w2s_al4(mask)) return CS_SCALAR;
-  return sm;
-}
-
 static size_t w2s_words_per_block(int k1) { return (size_t)(2 * k1 + 1) * 2 + k1 + 2; }
 
 extern "C" int mia_w2s_labels(const float* logits, const float* dyn_dev, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
@@ -393,8 +314,7 @@ extern "C" int mia_w2s_labels(const float* logits, const float* dyn_dev, int nb,
   MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0, "mia_w2s_labels: negative strides");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const LossGeom g{sn, sk, sp};
-  int sm = cs_mode(logits, g, k1);
-  if (hw % 4 != 0 || !w2s_al4(code)) sm = CS_SCALAR;  // four pixels per thread: 16-byte units in the logits, 4-byte words in the map
+  const int sm = px4_mode(logits, g, k1, hw, code, nullptr);  // four pixels per thread: one 4-byte word of the map
   CS_DISPATCH1(w2s_launch_labels, st, logits, dyn_dev, nb, hw, g, slabs, workspace, code);
   hipLaunchKernelGGL(w2s_count_kernel, dim3(1), dim3(256), 0, st, workspace, nb * slabs, kept);
   MIA_LAUNCH_CHECK();
@@ -404,25 +324,18 @@ extern "C" int mia_w2s_labels(const float* logits, const float* dyn_dev, int nb,
 extern "C" int mia_cutmix_perm(const float* x, const int* perm, const unsigned char* mask, float* out, int nb, int c, int64_t hw,
                                int64_t mask_sn, int64_t out_sn, int* bad_perm, void* stream) {
   MIA_CHECK_ARG(x && perm && mask && out && bad_perm, "mia_cutmix_perm: null pointer");
-  MIA_CHECK_ARG(nb > 0 && c > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)c * hw <= 0x7fffffff &&
-                    ceil_div64((int64_t)nb * c * hw, 256) <= 0x7fffffff,
-                "mia_cutmix_perm: bad shape nb=%d c=%d hw=%lld", nb, c, (long long)hw);
-  MIA_CHECK_ARG((mask_sn == 0 || mask_sn == hw) && out_sn >= (int64_t)c * hw, "mia_cutmix_perm: bad strides mask_sn=%lld out_sn=%lld",
-                (long long)mask_sn, (long long)out_sn);
-  const int64_t chw = (int64_t)c * hw;
-  const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + 4 * (uintptr_t)((int64_t)nb * chw);
-  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + 4 * (uintptr_t)((int64_t)(nb - 1) * out_sn + chw);
-  MIA_CHECK_ARG(o1 <= x0 || x1 <= o0, "mia_cutmix_perm: out overlaps x (an image is read after its partner may have been written)");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool wide = hw % 4 == 0 && out_sn % 4 == 0 && cs_al16(x) && cs_al16(out) && w2s_al4(mask);
-  const int64_t total = (int64_t)nb * (wide ? chw / 4 : chw);
-  const dim3 grid((unsigned)ceil_div64(total, 256)), blk(256);
   const unsigned* xi = reinterpret_cast<const unsigned*>(x);
   unsigned* o = reinterpret_cast<unsigned*>(out);
-  if (wide) hipLaunchKernelGGL(w2s_cutmix_kernel<true>, grid, blk, 0, st, xi, perm, mask, o, nb, hw, chw, mask_sn, out_sn, total, bad_perm);
-  else hipLaunchKernelGGL(w2s_cutmix_kernel<false>, grid, blk, 0, st, xi, perm, mask, o, nb, hw, chw, mask_sn, out_sn, total, bad_perm);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return px4_mix_launch("mia_cutmix_perm", x, x, mask, out, nb, c, hw, mask_sn, out_sn,
+                        [&](bool wide, dim3 grid, int64_t chw, int64_t total) -> int {
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(x), x1 = x0 + 4 * (uintptr_t)((int64_t)nb * chw);
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + 4 * (uintptr_t)((int64_t)(nb - 1) * out_sn + chw);
+    MIA_CHECK_ARG(o1 <= x0 || x1 <= o0, "mia_cutmix_perm: out overlaps x (an image is read after its partner may have been written)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (wide) hipLaunchKernelGGL(w2s_cutmix_kernel<true>, grid, dim3(256), 0, st, xi, perm, mask, o, nb, hw, chw, mask_sn, out_sn, total, bad_perm);
+    else hipLaunchKernelGGL(w2s_cutmix_kernel<false>, grid, dim3(256), 0, st, xi, perm, mask, o, nb, hw, chw, mask_sn, out_sn, total, bad_perm);
+    return MIA_OK;
+  });
 }
 
 extern "C" int mia_w2s_loss_workspace(int nb, int k1, int slabs) {
@@ -435,15 +348,11 @@ extern "C" int mia_w2s_loss_fwd(const float* logits, const unsigned char* code, 
                                 float smooth, float ce_weight, float dice_weight, int slabs, float* workspace, float* coef, float* out,
                                 long long* counts, int* bad_perm, void* stream) {
   MIA_CHECK_ARG(logits && code && workspace && coef && out && counts && bad_perm, "mia_w2s_loss_fwd: null pointer");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_w2s_loss_fwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
-  MIA_CHECK_ARG(nb > 0 && hw > 0 && slabs > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff &&
-                    (int64_t)nb * slabs * (int64_t)w2s_words_per_block(k1) <= 0x7fffffff,
-                "mia_w2s_loss_fwd: bad shape nb=%d hw=%lld slabs=%d", nb, (long long)hw, slabs);
-  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && (mask_sn == 0 || mask_sn == hw), "mia_w2s_loss_fwd: bad strides");
+  const LossGeom g{sn, sk, sp};
+  if (const int e = hl_check("mia_w2s_loss_fwd", nb, hw, k1, slabs, w2s_words_per_block(k1), g, nullptr, mask_sn)) return e;
   if (!mask || !perm) mask = nullptr, perm = nullptr;  // no mix: plain FixMatch
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LossGeom g{sn, sk, sp};
-  const int sm = w2s_mode(logits, g, k1, hw, code, mask);
+  const int sm = px4_mode(logits, g, k1, hw, code, mask);
   CS_DISPATCH1(w2s_launch_fwd, st, logits, code, mask, perm, nb, hw, mask_sn, g, slabs, workspace, bad_perm);
   CS_DISPATCH1(w2s_launch_finalize, st, workspace, nb * slabs, (double)nb * (double)hw, dyn_dev, smooth, ce_weight, dice_weight, out,
                counts, coef);
@@ -455,15 +364,11 @@ extern "C" int mia_w2s_loss_bwd(const float* logits, const unsigned char* code, 
                                 const float* coef, const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn,
                                 int64_t sk, int64_t sp, int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, void* stream) {
   MIA_CHECK_ARG(logits && code && coef && dlogits, "mia_w2s_loss_bwd: null pointer");
-  MIA_CHECK_ARG(k1 >= 1 && k1 <= LOSS_MAXK, "mia_w2s_loss_bwd: k1=%d not in [1,%d]", k1, LOSS_MAXK);
-  MIA_CHECK_ARG(nb > 0 && hw > 0 && hw <= 0x7fffffff && (int64_t)nb * hw <= 0x7fffffff, "mia_w2s_loss_bwd: bad shape nb=%d hw=%lld",
-                nb, (long long)hw);
-  MIA_CHECK_ARG(sn >= 0 && sk >= 0 && sp >= 0 && gsn >= 0 && gsk >= 0 && gsp >= 0 && (mask_sn == 0 || mask_sn == hw),
-                "mia_w2s_loss_bwd: bad strides");
+  const LossGeom g{sn, sk, sp}, gd{gsn, gsk, gsp};
+  if (const int e = hl_check("mia_w2s_loss_bwd", nb, hw, k1, 0, 0, g, &gd, mask_sn)) return e;
   if (!mask || !perm) mask = nullptr, perm = nullptr;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LossGeom g{sn, sk, sp}, gd{gsn, gsk, gsp};
-  int sm = w2s_mode(logits, g, k1, hw, code, mask);
+  int sm = px4_mode(logits, g, k1, hw, code, mask);
   if (cs_mode(dlogits, gd, k1) != sm) sm = CS_SCALAR;  // the gradient in the layout class of its logits, or one pixel at a time
   CS_DISPATCH1(w2s_launch_bwd, st, logits, code, mask, perm, coef, grad_out, dlogits, nb, hw, mask_sn, g, gd);
   MIA_LAUNCH_CHECK();

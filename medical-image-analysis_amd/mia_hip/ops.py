@@ -1978,6 +1978,36 @@ def _bcp_mask(who: str, mask: torch.Tensor, b: int, h: int, w: int):
     return mask.contiguous(), (h * w if mask.ndim == 3 else 0)
 
 
+def _mix_out(who: str, x: torch.Tensor, out: Optional[torch.Tensor], whose: str):
+    """(out, its image stride) of a mix of batches shaped like the contiguous `x`: a new tensor, or the caller's dense-image one."""
+    b, c, h, w = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or \
+            out.stride()[1:] != x.stride()[1:] or (b > 1 and out.stride(0) < c * h * w):
+        raise MiaError(f"{who}: `out` is fp32 of the {whose} shape with dense images (a batch slice of a contiguous tensor)")
+    return out, (out.stride(0) if b > 1 else c * h * w)
+
+
+def _hard_loss_logits(who: str, logits: torch.Tensor, limit: int):
+    """The opening of the hard-label losses (csrc/hard_loss.h): fp32 logits [B, K, H, W] with K <= limit through `_loss_logits`."""
+    if logits.ndim != 4:
+        raise NotImplementedError(f"the HIP {who} implements 2-D inputs [B, K, H, W]")
+    logits, st = _loss_logits(logits)
+    if not 1 <= logits.shape[1] <= limit:
+        raise MiaError(f"{who}: {logits.shape[1]} classes not in [1, {limit}] (the tensor-op form, fused=False, takes more)")
+    return logits, st
+
+
+def _hard_loss_buf(workspace: str, dev, b: int, k1: int, hw: int, ncoef: int, nout: int):
+    """(slabs, workspace, coef, out, counts) of a hard-label loss forward: workspace | coef | out are views of ONE fp32 allocation
+    whose every word the kernels write, `workspace` names the entry point that sizes it; counts is int64 [2]."""
+    slabs = _two_logits_slabs(hw)
+    words = max(getattr(lib(), workspace)(b, k1, slabs), 0)  # < 0: a bad shape, reported by the loss call
+    buf = torch.empty(words + ncoef + nout, device=dev, dtype=torch.float32)
+    return slabs, buf[:words], buf[words:words + ncoef], buf[words + ncoef:], torch.empty(2, device=dev, dtype=torch.int64)
+
+
 def bcp_mix(fg: torch.Tensor, bg: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[n, c, p] = fg[n, c, p] where mask[n or 0, p] != 0, else bg[n, c, p] (include/mia_hip.h: mia_bcp_mix; csrc/bcp.hip).
     fg, bg: contiguous fp32 [B, C, H, W]; mask: uint8 [H, W] or [B, H, W]; out: None (a new tensor) or fp32 [B, C, H, W] whose
@@ -1990,15 +2020,10 @@ def bcp_mix(fg: torch.Tensor, bg: torch.Tensor, mask: torch.Tensor, out: Optiona
                        f"and {tuple(bg.shape)} {bg.dtype}")
     b, c, h, w = fg.shape
     mask, msn = _bcp_mask("bcp_mix", mask, b, h, w)
-    if out is None:
-        out = torch.empty_like(fg)
-    elif out.shape != fg.shape or out.dtype != torch.float32 or out.device != fg.device or \
-            out.stride()[1:] != fg.stride()[1:] or (b > 1 and out.stride(0) < c * h * w):
-        raise MiaError("bcp_mix: `out` is fp32 of the inputs' shape with dense images (a batch slice of a contiguous tensor)")
+    out, osn = _mix_out("bcp_mix", fg, out, "inputs'")
     if fg.numel() == 0:
         return out
-    call("mia_bcp_mix", _p(fg.detach()), _p(bg.detach()), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn),
-         _c_i64(out.stride(0) if b > 1 else c * h * w), _stream())
+    call("mia_bcp_mix", _p(fg.detach()), _p(bg.detach()), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn), _c_i64(osn), _stream())
     return out
 
 
@@ -2014,12 +2039,8 @@ class CopyPasteLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, label_a, label_b, mask, weight_a: float, weight_b: float, smooth: float):
         _need_dev(logits, label_a, label_b, mask)
-        if logits.ndim != 4:
-            raise NotImplementedError("the HIP copy-paste loss implements 2-D inputs [B, K, H, W]")
-        logits, st = _loss_logits(logits)
+        logits, st = _hard_loss_logits("copy-paste loss", logits, BCP_MAX_CLASSES)
         b, k1, h, w = logits.shape
-        if not 1 <= k1 <= BCP_MAX_CLASSES:
-            raise MiaError(f"copy-paste loss: {k1} classes not in [1, {BCP_MAX_CLASSES}] (the tensor-op form, fused=False, takes more)")
         if label_a.numel() != b * h * w or label_b.numel() != b * h * w:
             raise MiaError(f"copy-paste loss: labels {tuple(label_a.shape)} / {tuple(label_b.shape)} do not index the pixels of "
                            f"logits {tuple(logits.shape)}")
@@ -2027,18 +2048,11 @@ class CopyPasteLossFn(torch.autograd.Function):
         label_a, label_b = (t.reshape(b, h, w) if u8 else t.reshape(b, h, w).long() for t in (label_a, label_b))
         label_a, label_b = label_a.contiguous(), label_b.contiguous()
         mask, msn = _bcp_mask("copy-paste loss", mask, b, h, w)
-        hw = h * w
-        dev = logits.device
-        slabs = _two_logits_slabs(hw)
-        words = max(lib().mia_bcp_loss_workspace(b, k1, slabs), 0)  # < 0: a bad shape, reported by the call below
-        ncoef = 4 * k1 + 2
-        buf = torch.empty(words + ncoef + 5, device=dev, dtype=torch.float32)  # workspace | coef | out[5]: every word written
-        ws, coef, out = buf[:words], buf[words:words + ncoef], buf[words + ncoef:]
-        counts = torch.empty(2, device=dev, dtype=torch.int64)
-        bad = _bad_flags(dev)
+        hw, dev = h * w, logits.device
+        slabs, ws, coef, out, counts = _hard_loss_buf("mia_bcp_loss_workspace", dev, b, k1, hw, 4 * k1 + 2, 5)
         call("mia_bcp_loss_fwd", _p(logits), _p(label_a), _p(label_b), _p(mask), b, _c_i64(hw), k1, *_strides_i64(st), _c_i64(msn),
-             int(u8), _c_float(smooth), _c_float(weight_a), _c_float(weight_b), slabs, _p(ws), _p(coef), _p(out), _p(counts), _p(bad),
-             _stream())
+             int(u8), _c_float(smooth), _c_float(weight_a), _c_float(weight_b), slabs, _p(ws), _p(coef), _p(out), _p(counts),
+             _p(_bad_flags(dev)), _stream())
         ctx.save_for_backward(logits, label_a, label_b, mask, coef)
         ctx.st, ctx.msn, ctx.u8 = st, msn, u8
         CopyPasteLossFn.last_out, CopyPasteLossFn.last_counts = out, counts
@@ -2145,15 +2159,11 @@ def cutmix_perm(x: torch.Tensor, perm, mask: torch.Tensor, out: Optional[torch.T
     b, c, h, w = x.shape
     perm = _perm_arg("cutmix_perm", perm, b, x.device)
     mask, msn = _bcp_mask("cutmix_perm", mask, b, h, w)
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or \
-            out.stride()[1:] != x.stride()[1:] or (b > 1 and out.stride(0) < c * h * w):
-        raise MiaError("cutmix_perm: `out` is fp32 of the input's shape with dense images (a batch slice of a contiguous tensor)")
+    out, osn = _mix_out("cutmix_perm", x, out, "input's")
     if x.numel() == 0:
         return out
-    call("mia_cutmix_perm", _p(x.detach()), _p(perm), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn),
-         _c_i64(out.stride(0) if b > 1 else c * h * w), _p(_perm_flags(x.device)), _stream())
+    call("mia_cutmix_perm", _p(x.detach()), _p(perm), _p(mask), _p(out), b, c, _c_i64(h * w), _c_i64(msn), _c_i64(osn),
+         _p(_perm_flags(x.device)), _stream())
     return out
 
 
@@ -2170,31 +2180,19 @@ class WeakToStrongFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, code, mask, perm, dyn, ce_weight: float, dice_weight: float, smooth: float):
         _need_dev(logits, code, mask, dyn)
-        if logits.ndim != 4:
-            raise NotImplementedError("the HIP weak-to-strong loss implements 2-D inputs [B, K, H, W]")
-        logits, st = _loss_logits(logits)
+        logits, st = _hard_loss_logits("weak-to-strong loss", logits, W2S_MAX_CLASSES)
         b, k1, h, w = logits.shape
-        if not 1 <= k1 <= W2S_MAX_CLASSES:
-            raise MiaError(f"weak-to-strong loss: {k1} classes not in [1, {W2S_MAX_CLASSES}] (the tensor-op form, fused=False, takes more)")
         if code.dtype != torch.uint8 or tuple(code.shape) != (b, h, w):
             raise MiaError(f"weak-to-strong loss: the code map is uint8 [{b}, {h}, {w}] (ops.w2s_labels), got {code.dtype} "
                            f"{tuple(code.shape)}")
-        code = code.contiguous()
-        dev = logits.device
-        msn = 0
+        code, dev, hw, msn = code.contiguous(), logits.device, h * w, 0
         if mask is None or perm is None:
             mask = perm = None
         else:
             mask, msn = _bcp_mask("weak-to-strong loss", mask, b, h, w)
             perm = _perm_arg("weak-to-strong loss", perm, b, dev)
         dyn = _dyn_arg("weak-to-strong loss", dyn, 2, True)
-        hw = h * w
-        slabs = _two_logits_slabs(hw)
-        words = max(lib().mia_w2s_loss_workspace(b, k1, slabs), 0)  # < 0: a bad shape, reported by the call below
-        ncoef = 2 * k1 + 1
-        buf = torch.empty(words + ncoef + 4, device=dev, dtype=torch.float32)  # workspace | coef | out[4]: every word written
-        ws, coef, out = buf[:words], buf[words:words + ncoef], buf[words + ncoef:]
-        counts = torch.empty(2, device=dev, dtype=torch.int64)
+        slabs, ws, coef, out, counts = _hard_loss_buf("mia_w2s_loss_workspace", dev, b, k1, hw, 2 * k1 + 1, 4)
         call("mia_w2s_loss_fwd", _p(logits), _p(code), _p(mask), _p(perm), _p(dyn), b, _c_i64(hw), k1, *_strides_i64(st), _c_i64(msn),
              _c_float(smooth), _c_float(ce_weight), _c_float(dice_weight), slabs, _p(ws), _p(coef), _p(out), _p(counts),
              _p(_perm_flags(dev)), _stream())
