@@ -775,6 +775,37 @@ int mia_w2s_loss_bwd(const float* logits, const unsigned char* code, const unsig
                      const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
                      int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, void* stream);
 
+/* ------------------------------------------------------------------ dual-task consistency (csrc/dtc.hip) */
+/* DTC (Luo et al., AAAI 2021; the reference has no such code; definition: losses/dual_task.py).  z: segmentation logits fp32
+ * [nb][k1][hw] by (sn, sk, sp), r: level-set logits fp32 [nb][k1 - 1][hw] by (rsn, rsk, rsp), each addressed like mia_consistency_fwd
+ * (planar, channels-last and scalar layout classes, batch slices); 2 <= k1 <= 8; channel c of r belongs to class c + 1.  The first lb
+ * images are labelled: phi is the contiguous fp32 [lb][k1 - 1][hw] map of mia_signed_distance_map at unit spacing, extent the
+ * [lb][k1 - 1][2] of mia_sdm_extent; both may be NULL when lb = 0.  With s = softmax(z), t = tanh(r), q = sigmoid(-k t) and the
+ * normalised target T = phi / m_out (phi > 0), -(1 - phi) / (1 + m_in) (phi < 0), 0 (phi = 0), computed per pixel and never stored:
+ *   L_cons = mean over all (n, c, p) of (q_c - s_{c+1})^2,   L_sdf = mean over (n < lb, c, p) of (t - T)^2   (0 when lb = 0)
+ *   L = dyn_dev[0] L_cons + dyn_dev[1] L_sdf     (dyn_dev NULL: 1, 1; read on the device when the kernels run)
+ * Soft-max, tanh and sigmoid are evaluated in double from the fp32 logits in a form that stays finite for |k t| in the thousands.
+ * A thread owns the same four consecutive pixels on the 16-byte path (z and r both planar / channels-last, hw % 4 == 0, 16-byte aligned
+ * phi; in the backward each gradient in the layout class of its logits) and on the scalar path, and every sum runs in one fixed order:
+ * the two paths give the same bits, and every result is bit-identical from run to run (no float atomics).  Limits: nb * hw < 2^31.
+ * Every check happens before any launch; nothing synchronises with the host. */
+/* extent [planes][2] = {max phi, max -phi} per plane of hw elements, both >= +0: integer max on the bit patterns of non-negative
+ * floats, exact and independent of the order.  planes * hw < 2^31. */
+int mia_sdm_extent(const float* phi, int planes, int64_t hw, float* extent, void* stream);
+/* The streaming pass: workspace [nb * slabs][2][2] receives the (hi, lo) float pairs of every block's sums of the two terms (slabs =
+ * blocks per image; nb * slabs * 4 4-byte words). */
+int mia_dtc_fwd(const float* z, const float* r, const float* phi, const float* extent, int nb, int lb, int64_t hw, int k1, float k,
+                int64_t sn, int64_t sk, int64_t sp, int64_t rsn, int64_t rsk, int64_t rsp, int slabs, float* workspace, void* stream);
+/* One block, in double, in a fixed order: out[3] = {L, L_cons, L_sdf}; coef[2] = {2 dyn[0] / (nb C hw), 2 dyn[1] / (lb C hw) or 0},
+ * each rounded once to fp32: what the backward reads. */
+int mia_dtc_finalize(const float* workspace, const float* dyn_dev, int nb, int lb, int64_t hw, int k1, int slabs, float* coef,
+                     float* out, void* stream);
+/* One pass: recomputes s, t, q and T; writes dz = grad_out dL/dz by (gsn, gsk, gsp) and dr = grad_out dL/dr by (hsn, hsk, hsp)
+ * (grad_out: device pointer to one float or NULL for 1).  dr of an image n >= lb has no L_sdf part. */
+int mia_dtc_bwd(const float* z, const float* r, const float* phi, const float* extent, const float* coef, const float* grad_out,
+                float* dz, float* dr, int nb, int lb, int64_t hw, int k1, float k, int64_t sn, int64_t sk, int64_t sp, int64_t rsn,
+                int64_t rsk, int64_t rsp, int64_t gsn, int64_t gsk, int64_t gsp, int64_t hsn, int64_t hsk, int64_t hsp, void* stream);
+
 /* ------------------------------------------------------------------ virtual adversarial training (csrc/vat.hip) */
 /* KL distance between two fp32 logits tensors [nb][k1][hw], each addressed by its own (sn, sk, sp) / (tsn, tsk, tsp) element strides
  * like mia_consistency_fwd (planar, channels-last and scalar layout classes, batch slices):

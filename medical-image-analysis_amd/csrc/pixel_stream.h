@@ -1,10 +1,10 @@
 // What the streaming losses over logits-shaped tensors share.  ONE definition of each piece, so that the files cannot drift apart
 // (loss_common.h, ds_common.h).
-//   consistency.hip, cps.hip, bcp.hip, w2s.hip   the layout classes of a logits-shaped tensor (cs_mode), the loads and stores of one
-//                                 thread's pixel group in each class (cs_load, cs_store), the per-pixel soft-max in double (cs_softmax)
-//   consistency.hip, cps.hip      the dispatch over (class count, layout class of the first tensor, of the second): CS_DISPATCH
+//   consistency.hip, cps.hip, bcp.hip, w2s.hip, dtc.hip   the layout classes of a logits-shaped tensor (cs_mode), the loads and stores of
+//                                 one thread's pixel group in each class (cs_load, cs_store), the per-pixel soft-max in double (cs_softmax)
+//   consistency.hip, cps.hip      the dispatch over (class count, layout class of the first, of the second tensor): CS_DISPATCH; dtc.hip: CS_MODES
 //   cps.hip, w2s.hip, hard_loss.h the hard-label pieces: cs_argmax, cs_nll_term, cs_max
-//   bcp.hip, w2s.hip              a thread that owns FOUR consecutive pixels on every path (px4_*, cs_park), the dispatch over (class
+//   bcp.hip, w2s.hip, dtc.hip     a thread that owns FOUR consecutive pixels on every path (px4_*; cs_park not in dtc.hip), the dispatch over (class
 //                                 count, layout class): CS_DISPATCH1, and the launch of a mix under a mask (px4_mix_launch); their
 //                                 Dice + CE core is hard_loss.h
 // The double-precision partial sums, which boundary.hip and urpc.hip use too, are in loss_common.h.

@@ -2214,6 +2214,91 @@ class WeakToStrongFn(torch.autograd.Function):
 WeakToStrongFn.last_out = WeakToStrongFn.last_counts = None
 
 
+# ------------------------------------------------------------------ dual-task consistency (level-set head against the soft-max)
+DTC_MAX_CLASSES = 8
+
+
+def sdm_extent(phi: torch.Tensor) -> torch.Tensor:
+    """fp32 `[..., 2]` = {max phi, max -phi} over the last two dims of a signed distance map `phi` [B, C, H, W], both >= +0
+    (include/mia_hip.h: mia_sdm_extent; csrc/dtc.hip): how far the map reaches outside and inside each object.  Integer max on the
+    bit patterns, so the result is exact and does not depend on the order.  No autograd, no host sync."""
+    _need_dev(phi)
+    if phi.ndim != 4 or phi.dtype != torch.float32:
+        raise MiaError(f"sdm_extent: an fp32 distance map [B, C, H, W] expected, got {tuple(phi.shape)} {phi.dtype}")
+    phi = phi.detach().contiguous()
+    b, c, h, w = phi.shape
+    ext = torch.empty((b, c, 2), device=phi.device, dtype=torch.float32)  # zeroed and filled by the call
+    if phi.numel() == 0:
+        return ext.zero_()
+    call("mia_sdm_extent", _p(phi), b * c, _c_i64(h * w), _p(ext), _stream())
+    return ext
+
+
+class DTCLossFn(torch.autograd.Function):
+    """`apply(z, r, phi, extent, lb, k, dyn)` -> the dual-task consistency loss (include/mia_hip.h: mia_dtc_fwd; csrc/dtc.hip; the
+    definition is the module text of losses/dual_task.py): `dyn[0] * L_cons + dyn[1] * L_sdf` between the segmentation logits `z`
+    [B, K, H, W] and the level-set logits `r` [B, K - 1, H, W], both fp32 in any layout whose H and W collapse, 2 <= K <= 8.  The
+    first `lb` images are labelled: `phi` is their fp32 signed distance map [lb, K - 1, H, W] at unit spacing (`signed_distance_map`)
+    and `extent` its `sdm_extent` (None: computed here); with `lb = 0` both may be None.  One streaming forward pass and one streaming
+    backward pass; `z` and `r` get a gradient, `phi` none.  `dyn` is None (both weights 1) or the DEVICE fp32 {consistency weight,
+    beta} that the kernels read when they run.  By-product of the latest forward, on the device: `last_out` = {L, L_cons, L_sdf}."""
+
+    @staticmethod
+    def forward(ctx, z, r, phi, extent, lb: int, k: float, dyn):
+        _need_dev(z, r, phi, extent, dyn)
+        if z.ndim != 4 or r.ndim != 4:
+            raise NotImplementedError("the HIP dual-task loss implements 2-D inputs [B, K, H, W]")
+        z, st = _loss_logits(z)
+        r, rt = _loss_logits(r)
+        b, k1, h, w = z.shape
+        if not 2 <= k1 <= DTC_MAX_CLASSES:
+            raise MiaError(f"dual-task loss: {k1} classes not in [2, {DTC_MAX_CLASSES}] (the tensor-op form, fused=False, takes more)")
+        if tuple(r.shape) != (b, k1 - 1, h, w):
+            raise MiaError(f"dual-task loss: level-set logits {tuple(r.shape)}, expected {(b, k1 - 1, h, w)} for logits {tuple(z.shape)}")
+        lb = int(lb)
+        if not 0 <= lb <= b:
+            raise MiaError(f"dual-task loss: labeled_bs={lb} not in [0, {b}]")
+        if lb > 0:
+            if phi is None or tuple(phi.shape) != (lb, k1 - 1, h, w) or phi.dtype != torch.float32:
+                raise MiaError(f"dual-task loss: the distance map of the {lb} labelled images is fp32 {(lb, k1 - 1, h, w)}, got "
+                               f"{None if phi is None else (tuple(phi.shape), phi.dtype)}")
+            phi = phi.detach().contiguous()
+            if extent is None:
+                extent = sdm_extent(phi)
+            elif tuple(extent.shape) != (lb, k1 - 1, 2) or extent.dtype != torch.float32:
+                raise MiaError(f"dual-task loss: extents {tuple(extent.shape)} {extent.dtype}, expected fp32 {(lb, k1 - 1, 2)}")
+            extent = extent.detach().contiguous()
+        else:
+            phi = extent = None
+        dyn = _dyn_arg("dual-task loss", dyn, 2, True)
+        hw, dev = h * w, z.device
+        slabs = _two_logits_slabs(hw)
+        words = max(b * slabs * 4, 0)
+        buf = torch.empty(words + 5, device=dev, dtype=torch.float32)  # workspace | out[3] | coef[2]: one allocation, every word written
+        ws, out, coef = buf[:words], buf[words:words + 3], buf[words + 3:]
+        call("mia_dtc_fwd", _p(z), _p(r), _p(phi), _p(extent), b, lb, _c_i64(hw), k1, _c_float(k), *_strides_i64(st),
+             *_strides_i64(rt), slabs, _p(ws), _stream())
+        call("mia_dtc_finalize", _p(ws), _p(dyn), b, lb, _c_i64(hw), k1, slabs, _p(coef), _p(out), _stream())
+        ctx.save_for_backward(z, r, coef)
+        ctx.phi, ctx.extent, ctx.lb, ctx.k, ctx.st, ctx.rt = phi, extent, lb, float(k), st, rt
+        DTCLossFn.last_out = out
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, r, coef = ctx.saved_tensors
+        b, k1, h, w = z.shape
+        dz, gst, g = _loss_bwd_begin(z, gout)
+        dr = torch.empty_like(r)
+        call("mia_dtc_bwd", _p(z), _p(r), _p(ctx.phi), _p(ctx.extent), _p(coef), _p(g), _p(dz), _p(dr), b, ctx.lb, _c_i64(h * w), k1,
+             _c_float(ctx.k), *_strides_i64(ctx.st), *_strides_i64(ctx.rt), *_strides_i64(gst), *_strides_i64(_pix_strides(dr)),
+             _stream())
+        return dz, dr, None, None, None, None, None
+
+
+DTCLossFn.last_out = None
+
+
 # ------------------------------------------------------------------ region-based loss (sigmoid soft Dice + BCE)
 REGLOSS_MAX_CHANNELS = 8
 

@@ -55,6 +55,14 @@ unlabelled batch from the loader; the mix is a selection, not a blend; the box a
 instead of redrawn until it does; the CE denominator is always the pixel count, where UniMatch divides by the kept pixels.  Out of
 scope: UniMatch's feature-perturbation stream (Dropout2d on the skips between encoder and decoder), graph capture, more than one
 rank, 3-D.
+
+`DTCEngine` is dual-task consistency (DTC: Luo et al., AAAI 2021): one network with TWO 1x1 heads on the last decoder activation
+(`models.unet.DualTaskUNet`), the segmentation logits and a level-set map -- `tanh` of a regression of the normalised signed distance
+to the object boundary.  On the labelled images the level-set head regresses the target that `signed_distance_map` and
+`ops.sdm_extent` give from the labels the step sees; on EVERY image `sigmoid(-1500 tanh)` of the level-set head must agree with the
+soft-max of the segmentation head (`losses.dual_task.DualTaskConsistencyLoss`, csrc/dtc.hip).  No teacher, no extra pass: one
+training forward of the whole batch.  Same batch convention; `dyn = {consistency weight, beta}`; eager, one rank, 2-D inputs, index
+labels.  Out of scope: 3-D, graph capture, a pixel spacing other than 1, a level-set head on a subset of the classes.
 """
 from __future__ import annotations
 
@@ -821,3 +829,61 @@ class FixMatchEngine(SemiEngine):
         self.last_unsup, self.last_code = unsup.detach(), code
         self.last_masks, self.last_perms, self.last_net_in = masks, perms, net_in
         return sup + unsup
+
+
+class DTCEngine(SemiEngine):
+    """one network with a segmentation head and a level-set head + supervised loss on the labelled images + dual-task consistency on
+    all of them + flat optimizer + poly LR.  `train_step` returns the loss TENSOR (no host sync); `last_supervised`,
+    `last_consistency` and `last_sdf` (both unweighted) are device by-products of the latest step.  With lb = labeled_bs, one step is
+
+        z, r = model(image, return_level_set=True)          ONE training forward of the whole batch; both heads are `ops.HeadFn` on
+                                                            the last decoder activation
+        loss = supervised_loss(z[:lb], label[:lb]) + dtc(z, r, label, lb, dyn=dyn)
+             = supervised + dyn[0] * L_cons(all images) + dyn[1] * L_sdf(labelled images)
+
+    where the loss computes `phi = signed_distance_map(label[:lb], K - 1)` and its extents on the device, every step, from the labels
+    it is given (`losses/dual_task.py` is the definition).  A batch without unlabelled images still has both terms.
+    model: a `models.unet.DualTaskUNet`; a plain `UNet` has no `decoder.ls_output` and is refused.
+    dtc: None = `DualTaskConsistencyLoss(K - 1)`; a module with that call signature.  False is refused: without the term the
+    level-set head is never trained, and a supervised engine says that better.
+    consistency_weight, beta: a float or an object with `.step(i)`; each step the engine writes both into the device buffer `dyn`
+    before anything reads it, outside the autograd graph.  The published values are a sigmoid ramp to 0.1 and 0.3.
+    The checkpoint is the base engine's: the extra head is in the model's `state_dict`.  Eager steps, one rank, 2-D inputs."""
+
+    def __init__(self, model, supervised_loss, labeled_bs: int, dtc=None, consistency_weight=0.1, beta=0.3,
+                 optimizer_name: str = "adam", optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000,
+                 lr_warmup_iter: int = 250, lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0,
+                 process_group=None):
+        if getattr(getattr(model, "decoder", None), "ls_output", None) is None:
+            raise ValueError("DTCEngine needs a model with a level-set head (models.unet.DualTaskUNet): a plain UNet has no "
+                             "decoder.ls_output, and the dual-task term compares the two heads")
+        if dtc is False:
+            raise ValueError("DTCEngine: dtc=False would train without the dual-task term and leave the level-set head untrained; "
+                             "use a supervised engine for that")
+        super().__init__(model, labeled_bs, grad_norm, process_group, optimizer_name, optimizer_kwargs, start_lr, num_iters,
+                         lr_warmup_iter, lr_interval, lr_scheduler_name)
+        self.supervised_loss = supervised_loss
+        self.consistency_weight, self.beta = consistency_weight, beta
+        self.num_classes = int(model.decoder.seg_output.weight.shape[0])  # K: background included
+        if int(model.decoder.ls_output.weight.shape[0]) != self.num_classes - 1:
+            raise ValueError(f"DTCEngine: the level-set head has {int(model.decoder.ls_output.weight.shape[0])} channels for "
+                             f"{self.num_classes - 1} foreground classes")
+        if dtc is None:
+            from losses.dual_task import DualTaskConsistencyLoss
+            dtc = DualTaskConsistencyLoss(self.num_classes - 1)
+        self.dtc = dtc
+        self.last_supervised = self.last_consistency = self.last_sdf = None
+
+    def _dyn_values(self):
+        return _ramp_value(self.consistency_weight, self.current_iter), _ramp_value(self.beta, self.current_iter)
+
+    def _loss(self, image: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
+        lb = self.labeled_bs
+        self._write_dyn()
+        z, r = self.model(image, return_level_set=True)
+        sup = self.supervised_loss(z[:lb], label[:lb])
+        self.last_supervised = sup.detach()
+        loss = sup + self.dtc(z, r, label, lb, dyn=self.dyn)
+        self.last_consistency = getattr(self.dtc, "last_consistency", None)
+        self.last_sdf = getattr(self.dtc, "last_sdf", None)
+        return loss
