@@ -3,9 +3,9 @@
 // Reference: ALTrainer.train_step (src/training/al_trainer.py:1374-1379): zero_grad, backward,
 // clip_grad_norm_(params, 10.0), optimizer.step() with torch.optim.Adam / AdamW(betas=(0.9,0.999)) or
 // SGD(momentum=0.9) (al_trainer.py:744-761).  All parameters / gradients / moments live in ONE flat
-// fp32 buffer each, so the global L2 norm is one two-stage reduction and the update is one 16-byte
-// vectorised stream (4 reads + 3 writes per element) with the clip coefficient read from device
-// memory -- no host synchronisation anywhere in the step.
+// fp32 buffer each, so the global L2 norm is one two-stage reduction (16-byte loads) and the update is
+// one grid-stride stream of scalar 4-byte accesses (4 reads + 3 writes per element, coalesced across a
+// wave) with the clip coefficient read from device memory -- no host synchronisation anywhere in the step.
 #include "common.h"
 
 __global__ void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
