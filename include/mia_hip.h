@@ -774,6 +774,33 @@ int mia_w2s_loss_fwd(const float* logits, const unsigned char* code, const unsig
 int mia_w2s_loss_bwd(const float* logits, const unsigned char* code, const unsigned char* mask, const int* perm, const float* coef,
                      const float* grad_out, float* dlogits, int nb, int64_t hw, int k1, int64_t sn, int64_t sk, int64_t sp,
                      int64_t gsn, int64_t gsk, int64_t gsp, int64_t mask_sn, void* stream);
+/* UniMatch's feature-perturbation stream (csrc/feat_drop.hip; the reference has no such code): the decoder reads an encoder output x
+ * [n][hw][c] (contiguous NHWC, dtype MIA_F32 or MIA_BF16) followed along the batch axis by channel-dropped copies of its rows row0 ..
+ * row0 + nu - 1.  mask: fp32 [nu][c], any values (Dropout2d: 0 or 1 / (1 - p)), 0 = dropped; out / dy: contiguous [n + nu][hw][c].
+ *   forward   out[i] = x[i] (bit copy, i < n);   out[n + u] = m[u][ch] == 0 ? +0.0 : rnd(x[row0 + u] * m[u][ch])        (u < nu)
+ *   backward  dx[i] = dy[i] (bit copy) where i is outside [row0, row0 + nu) or m[i - row0][ch] == 0, otherwise
+ *             dx[i] = rnd(dy[i] + rnd(dy[n + i - row0] * m[i - row0][ch]))
+ * The product is formed in fp32; rnd is the identity for fp32 and round-to-nearest-even for bf16.  A dropped channel is a SELECTION,
+ * like mia_bcp_mix / mia_cutmix_perm: a NaN or inf under it does not spread, the forward gives +0.0 (never -0.0), the backward passes
+ * dy[i]'s bits through.  In the backward the product and the sum are TWO separately rounded operations, never one fused multiply-add:
+ * dx has the bits of the tensor-op form `cat(x, where(m == 0, 0, x[rows].float() * m).to(dtype))` under autograd, which multiplies in
+ * one kernel -- and, for bf16, rounds the product to bf16 where the gradient of the cast leaves fp32 -- and adds in another.
+ * amax_out: NULL, or (fp32 only; ignored for bf16) a ZEROED 4-byte slot that receives max |out| / max |dx| as an fp32 bit pattern --
+ * the amax_out convention of the norm kernels: an integer maximum of the bit patterns of |v|, exact and independent of the order, no
+ * float atomics; a NaN counts as mia_amax counts it.  Each pass reads and writes every element once: (2 n + nu) hw c elements of
+ * traffic; the work item that reads a row of [row0, row0 + nu) writes (forward) or reads (backward) both of its images.  16-byte
+ * accesses (4 fp32 / 8 bf16 channels of one pixel, the mask as aligned float4 loads) when c * element size is a multiple of 16 and
+ * x / dy, out / dx and mask are 16-byte aligned; one element per thread otherwise; both give the same bits, and every result is
+ * bit-identical from run to run.  Element counts are 64-bit; the grid is capped and a block strides over tiles of whole pixels.
+ * Errors (< 0, nothing is launched): nu < 1, row0 < 0, row0 + nu > n, c < 1, hw < 1, a bad dtype, a NULL x / dy, mask or out / dx,
+ * out overlapping x (dx overlapping dy).  Nothing synchronises with the host. */
+int mia_feat_drop_cat_fwd(int dtype, const void* x, const float* mask, void* out, int n, int64_t hw, int c, int row0, int nu,
+                          void* amax_out, void* stream);
+int mia_feat_drop_cat_bwd(int dtype, const void* dy, const float* mask, void* dx, int n, int64_t hw, int c, int row0, int nu,
+                          void* amax_out, void* stream);
+/* The launch shape, for tests and byte counts: returns the block cap of the grid (> 0) and sets tile_pixels[0] to the pixels one block
+ * handles per stride on the 16-byte (wide != 0) or the one-element path; < 0 for bad arguments. */
+int mia_feat_drop_cat_sweep(int dtype, int c, int wide, int* tile_pixels);
 
 /* ------------------------------------------------------------------ dual-task consistency (csrc/dtc.hip) */
 /* DTC (Luo et al., AAAI 2021; the reference has no such code; definition: losses/dual_task.py).  z: segmentation logits fp32

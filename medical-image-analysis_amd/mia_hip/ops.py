@@ -683,6 +683,70 @@ def dropout_mask(numel: int, keep: float, device) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ UniMatch's feature perturbation: cat(x, Dropout2d(x[rows]))
+def _feat_drop_check(x: torch.Tensor, mask: torch.Tensor, row0: int) -> Tuple[int, int]:
+    if x.ndim != 4:
+        raise MiaError(f"feature_dropout_cat: x must be an NHWC activation [N, H, W, C], got {tuple(x.shape)}")
+    if mask.ndim != 2 or mask.shape[1] != x.shape[3] or mask.dtype != torch.float32 or mask.device != x.device:
+        raise MiaError(f"feature_dropout_cat: mask must be fp32 [nu, {x.shape[3]}] on {x.device}, got {mask.dtype} "
+                       f"{tuple(mask.shape)} on {mask.device}")
+    row0, nu = int(row0), int(mask.shape[0])
+    if nu < 1 or row0 < 0 or row0 + nu > x.shape[0]:
+        raise MiaError(f"feature_dropout_cat: rows [{row0}, {row0} + {nu}) outside the {x.shape[0]} images")
+    return row0, nu
+
+
+def feature_dropout_cat_tensor_ops(x: torch.Tensor, mask: torch.Tensor, row0: int) -> torch.Tensor:
+    """The definition of `feature_dropout_cat` in tensor ops (any device, any floating dtype): x followed along the batch axis by
+    the channel-dropped copies of its rows row0 .. row0 + nu - 1; the product is formed in fp32 (float64 for a float64 x) and a
+    dropped channel is a selection."""
+    row0, nu = _feat_drop_check(x, mask, row0)
+    m = mask[:, None, None, :]
+    wide = torch.float64 if x.dtype == torch.float64 else torch.float32
+    return torch.cat((x, torch.where(m == 0, 0, x[row0:row0 + nu].to(wide) * m).to(x.dtype)))
+
+
+class FeatDropCatFn(torch.autograd.Function):
+    """out [N + nu, H, W, C] = cat(x, Dropout2d(x[row0 : row0 + nu])) in ONE pass over x, and its gradient in one pass over dy
+    (include/mia_hip.h: mia_feat_drop_cat_fwd / _bwd; csrc/feat_drop.hip).  x: contiguous NHWC fp32 / bf16; mask: fp32 [nu, C] of
+    {0, 1 / (1 - p)} (any values; 0 = dropped).  The output is an ordinary tensor: it carries no `_mia_dup` tag, whatever x carries."""
+
+    @staticmethod
+    def forward(ctx, x, mask, row0: int):
+        ctx.set_materialize_grads(False)
+        _need_dev(x, mask)
+        row0, nu = _feat_drop_check(x, mask, row0)
+        x, mask = x.contiguous(), mask.contiguous()
+        n, h, w, c = x.shape
+        out = torch.empty((n + nu, h, w, c), device=x.device, dtype=x.dtype)
+        call("mia_feat_drop_cat_fwd", _dt(x), _p(x), _p(mask), _p(out), n, _c_i64(h * w), c, row0, nu, _p(_amax_new(out)), _stream())
+        ctx.save_for_backward(mask)
+        ctx.row0 = row0
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return None, None, None
+        (mask,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        nu = mask.shape[0]
+        n, (h, w, c) = dy.shape[0] - nu, dy.shape[1:]
+        dx = torch.empty((n, h, w, c), device=dy.device, dtype=dy.dtype)
+        call("mia_feat_drop_cat_bwd", _dt(dy), _p(dy), _p(mask), _p(dx), n, _c_i64(h * w), c, ctx.row0, nu, _p(_amax_new(dx)), _stream())
+        return dx, None, None
+
+
+def feature_dropout_cat(x: torch.Tensor, mask: torch.Tensor, row0: int, *, fused: bool = True) -> torch.Tensor:
+    """UniMatch's feature-perturbation input of the decoder for one encoder output: the N rows of x followed by the perturbed twins
+    of rows row0 .. row0 + nu - 1, `cat(x, Dropout2d(x[row0 : row0 + nu]))`.  x: NHWC activation; mask: fp32 [nu, C] on x's device.
+    fused=True: the HIP kernels (fp32 / bf16 on the device; no fallback); fused=False: `feature_dropout_cat_tensor_ops`, the same
+    definition under autograd, which also serves CPU tensors and other dtypes.  Both give the same bits, forward and gradient."""
+    if fused:
+        return FeatDropCatFn.apply(x, mask, row0)
+    return feature_dropout_cat_tensor_ops(x, mask, row0)
+
+
 # ------------------------------------------------------------------ PlainBlock: conv3x3 -> dropout2d -> norm -> lrelu
 class NormCfg:
     __slots__ = ("mode", "training", "eps", "momentum", "running_mean", "running_var", "num_batches", "drop_scale", "sync")

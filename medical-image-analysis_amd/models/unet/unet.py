@@ -201,30 +201,75 @@ class UNet(nn.Module):
             return self.encoder.forward_nhwc(ops.to_nhwc(x, torch.float32), self.compute_dtype)
         return self.encoder.forward_nhwc(ops.to_nhwc(x, self.compute_dtype), self.compute_dtype)
 
-    def _draw_dropout(self, n: int, device) -> None:
+    def _draw_dropout(self, n: int, device, n_dec: int = None) -> None:
         """All Dropout2d channel masks of this forward ([N, C] of {0, 1/(1-p)} per PlainBlock, blocks.py:92-96) from ONE
-        launch of the library's Philox mask kernel instead of one per block; a block without a pooled mask draws its own."""
+        launch of the library's Philox mask kernel instead of one per block; a block without a pooled mask draws its own.
+        n_dec: the images the DECODER's blocks see when that is not n (the feature-perturbation stream of `forward`)."""
         if not self.training:
             return
         blocks = [m for m in self.modules() if isinstance(m, PlainBlock) and m.dropout_prob and m.drop_mask_override is None]
         if len(blocks) < 2 or any(b.dropout_prob != blocks[0].dropout_prob for b in blocks):
             return
         keep = 1.0 - float(blocks[0].dropout_prob)
-        sizes = [n * b.all[2].num_features for b in blocks]
+        in_dec = set() if n_dec is None else {id(m) for m in self.decoder.modules()}
+        rows = [n_dec if id(b) in in_dec else n for b in blocks]
+        sizes = [r * b.all[2].num_features for r, b in zip(rows, blocks)]
         pool = ops.dropout_mask(sum(sizes), keep, device)
         off = 0
-        for b, sz in zip(blocks, sizes):
-            b._drop_from_pool = pool[off:off + sz].view(n, -1)
+        for b, r, sz in zip(blocks, rows, sizes):
+            b._drop_from_pool = pool[off:off + sz].view(r, -1)
             off += sz
 
-    def forward(self, x, return_ds=False, upsample_ds=True):
+    def _fp_masks(self, fp_rows, fp_drop: float, fp_masks, device):
+        """(row0, nu, one fp32 [nu, C_l] mask of {0, 1 / (1 - fp_drop)} per encoder level): the given ones, or all levels' from ONE
+        `ops.dropout_mask` call of nu * sum C_l values, split by level in encoder order."""
+        row0, nu = (int(v) for v in fp_rows)
+        chans = list(self.encoder.channels_list)
+        if fp_masks is not None:
+            masks = [m.to(device=device, dtype=torch.float32).contiguous() for m in fp_masks]
+            if [tuple(m.shape) for m in masks] != [(nu, c) for c in chans]:
+                raise ValueError(f"fp_masks must be one [{nu}, C_l] tensor per encoder level, C_l = {chans}; got "
+                                 f"{[tuple(m.shape) for m in masks]}")
+            return row0, nu, masks
+        if not 0.0 <= float(fp_drop) < 1.0:
+            raise ValueError(f"fp_drop must lie in [0, 1), got {fp_drop}")
+        pool = ops.dropout_mask(nu * sum(chans), 1.0 - float(fp_drop), device)
+        masks, off = [], 0
+        for c in chans:
+            masks.append(pool[off:off + nu * c].view(nu, c))
+            off += nu * c
+        return row0, nu, masks
+
+    def forward(self, x, return_ds=False, upsample_ds=True, *, fp_rows=None, fp_drop=0.5, fp_masks=None, fp_fused=True):
         """return_ds: [main logits] + the auxiliary heads' outputs, finest first; with upsample_ds=False those stay at their own
-        (lower) resolution, which is what `losses.deep_supervision.DeepSupervisionLoss` takes."""
+        (lower) resolution, which is what `losses.deep_supervision.DeepSupervisionLoss` takes.
+
+        fp_rows = (row0, nu): UniMatch's feature-perturbation stream (Yang et al., CVPR 2023).  For every encoder output f_l, the
+        bottleneck included, the decoder reads `cat(f_l, Dropout2d(fp_drop)(f_l[row0 : row0 + nu]))` along the batch axis
+        (`ops.feature_dropout_cat`; fp_fused=False: its tensor-op form, same bits) in ONE decoder pass, and the result is [N + nu, K,
+        H, W] logits: the N clean rows, then the perturbed twins of rows row0 .. row0 + nu - 1.  With batch norm the decoder's
+        statistics therefore span clean and perturbed rows, as in the published code.  The perturbation is an explicit argument, not
+        a module: it is applied in train() and eval() alike.  fp_masks: one [nu, C_l] tensor of {0, 1 / (1 - p)} per encoder level,
+        encoder order (parity runs, like `drop_mask_override`); without it all levels' masks come from ONE `ops.dropout_mask` call,
+        made after the blocks' own Dropout2d draw and before the encoder runs.  The blocks' own Dropout2d pool: the decoder's blocks
+        see N + nu images in this forward, and their share of the pooled draw is SIZED for that (each of the N + nu rows has its own
+        channel mask; no block falls back to a draw of its own).  `return_ds=True` is not implemented together with fp_rows.
+        fp_rows=None is the forward without the stream, bit for bit and draw for draw."""
         ops._COLSUM_HINT.clear()  # hints are only valid inside the backward pass of the forward that produced them
         ops._ACC_HINT.clear()
         ops._CR_HINT.clear()
-        self._draw_dropout(x.shape[0], x.device)
-        return self.decoder.forward_nhwc(self._skips(x), return_ds=return_ds, upsample_ds=upsample_ds)
+        if fp_rows is None:
+            self._draw_dropout(x.shape[0], x.device)
+            return self.decoder.forward_nhwc(self._skips(x), return_ds=return_ds, upsample_ds=upsample_ds)
+        if return_ds:
+            raise NotImplementedError("UNet.forward: return_ds=True is not implemented together with fp_rows")
+        row0, nu = (int(v) for v in fp_rows)
+        if nu < 1 or row0 < 0 or row0 + nu > x.shape[0]:
+            raise ValueError(f"fp_rows={tuple(fp_rows)}: rows [{row0}, {row0} + {nu}) outside the {x.shape[0]} images")
+        self._draw_dropout(x.shape[0], x.device, n_dec=x.shape[0] + nu)
+        row0, nu, masks = self._fp_masks(fp_rows, fp_drop, fp_masks, x.device)
+        skips = [ops.feature_dropout_cat(f, m, row0, fused=fp_fused) for f, m in zip(self._skips(x), masks)]
+        return self.decoder.forward_nhwc(skips, upsample_ds=upsample_ds)
 
     def get_enc_feature(self, x):
         return ops.global_avg_pool(self._skips(x)[-1])

@@ -748,17 +748,42 @@ class FixMatchEngine(SemiEngine):
     strong_transform: called as `strong_transform(U, zero labels)` -- a `BatchedAugment` with `inplace=False` and no resize, or any
     callable of that signature; the result is a dict with "image" or the image tensor itself, and must have U's shape.
     loss: None = `WeakToStrongLoss(K - 1, ce_weight, dice_weight)`; a module with that call signature; False = no unsupervised term.
-    The checkpoint is the base engine's: there is no extra state."""
+    The checkpoint is the base engine's: there is no extra state.
+
+    feature_perturbation=True adds UniMatch's third unlabelled stream (Yang et al., CVPR 2023): the decoder also runs on
+    channel-dropped copies of the weak rows' encoder outputs (`UNet.forward(fp_rows=...)`, Dropout2d(fp_drop) on every skip tensor
+    and the bottleneck), and the weak rows ride in the ONE student forward.  With N = lb + nu + V nu, one step is then
+
+        net_in = [ image[:lb] ; U ; view_0 ; .. ; view_{V-1} ]          N rows, ONE input (`last_net_in`), ONE forward
+        out    = model(net_in, fp_rows=(lb, nu), fp_drop=fp_drop)        [N + nu, K, H, W]
+        zw     = out[lb : lb + nu].detach();   code, kept = ops.w2s_labels(zw, dyn)
+        strong_v = w2s(out[lb + nu + v nu : lb + nu + (v + 1) nu], code, mask_v, perm_v, dyn=dyn)
+        fp       = w2s(out[N : N + nu], code, dyn=dyn)                   no mix: pixel p of a perturbed row is pixel p of its weak row
+        loss = supervised_loss(out[:lb], label[:lb]) + (1 - fp_weight) (1/V) sum_v strong_v + fp_weight fp
+
+    V = 2 and fp_weight = 0.5 give the paper's 0.25 / 0.25 / 0.5 split of the unlabelled term.  The paper's overall (L_x + L_u) / 2
+    is a scale of the learning rate and is not reproduced.  `last_fp` is the term as it enters the loss (fp_weight fp), `last_unsup`
+    the whole unlabelled term; `loss` has the bits of `last_supervised + last_unsup`.  Differences from the flag-off step: there is no
+    separate no-gradient weak pass -- the weak prediction is made inside the student's forward in train mode, so under batch norm it
+    uses THIS batch's statistics (spanning labelled, weak, strong and, in the decoder, perturbed rows) instead of the weak batch's
+    own, and it moves the running statistics; it is subject to the blocks' own dropout, as it already was.  The clean weak rows
+    enter no loss term, so the decoder's backward carries zero gradients for them (their encoder work is what the new stream trains
+    on).  The model must accept `fp_rows` / `fp_drop` (`models.unet.UNet`).  Eager steps, one rank, 2-D, like the rest of the engine."""
 
     def __init__(self, model, supervised_loss, labeled_bs: int, u_weight=1.0, confidence_threshold=0.95, strong_views: int = 1,
                  strong_transform=None, cutmix_prob: float = 0.5, cutmix_size=(0.02, 0.4), cutmix_ratio=(0.3, 1 / 0.3), loss=None,
                  ce_weight: float = 1.0, dice_weight: float = 0.0, optimizer_name: str = "adam",
                  optimizer_kwargs: Optional[dict] = None, start_lr: float = 1e-3, num_iters: int = 4000, lr_warmup_iter: int = 250,
-                 lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None):
+                 lr_interval: int = 1, lr_scheduler_name: str = "poly", grad_norm: float = 10.0, process_group=None,
+                 feature_perturbation: bool = False, fp_drop: float = 0.5, fp_weight: float = 0.5):
         if strong_views < 1:
             raise ValueError("FixMatchEngine: strong_views must be at least 1")
         if not 0.0 <= cutmix_prob <= 1.0:
             raise ValueError("FixMatchEngine: cutmix_prob must lie in [0, 1]")
+        if not 0.0 <= fp_weight <= 1.0:
+            raise ValueError("FixMatchEngine: fp_weight must lie in [0, 1]")
+        if not 0.0 <= fp_drop < 1.0:
+            raise ValueError("FixMatchEngine: fp_drop must lie in [0, 1)")
         if getattr(strong_transform, "inplace", False):
             raise ValueError("FixMatchEngine: strong_transform must not work in place (the unlabelled images are the weak view, and "
                              "every strong view starts from them)")
@@ -773,7 +798,8 @@ class FixMatchEngine(SemiEngine):
             from losses.weak_strong import WeakToStrongLoss
             loss = WeakToStrongLoss(self.num_classes - 1, ce_weight, dice_weight)
         self.w2s = loss or None
-        self.last_supervised = self.last_unsup = self.last_kept = self.last_code = None
+        self.feature_perturbation, self.fp_drop, self.fp_weight = bool(feature_perturbation), float(fp_drop), float(fp_weight)
+        self.last_supervised = self.last_unsup = self.last_kept = self.last_code = self.last_fp = None
         self.last_masks = self.last_perms = self.last_net_in = None
 
     def _dyn_values(self):
@@ -801,31 +827,44 @@ class FixMatchEngine(SemiEngine):
         self._write_dyn()
         image = image.contiguous()
         unlabeled = image[lb:]
-        with torch.no_grad(), ops.no_bn_tracking():
-            zw = self.model(unlabeled)
-        code, self.last_kept = ops.w2s_labels(zw, self.dyn)
+        fp = self.feature_perturbation
+        if not fp:
+            with torch.no_grad(), ops.no_bn_tracking():
+                zw = self.model(unlabeled)
+            code, self.last_kept = ops.w2s_labels(zw, self.dyn)
         views = self.strong_views
         h, w = image.shape[2:]
         dev = image.device
-        net_in = torch.empty((lb + views * nu,) + tuple(image.shape[1:]), device=dev, dtype=torch.float32)
+        first = lb + nu if fp else lb  # the first strong row: with the feature-perturbation stream the weak rows ride in the forward
+        rows = first + views * nu
+        net_in = torch.empty((rows,) + tuple(image.shape[1:]), device=dev, dtype=torch.float32)
         masks, perms = [], []
         for v in range(views):
             strong = self._strong(unlabeled)
             mask = box_masks(random_cutmix_boxes(nu, h, w, self.cutmix_prob, self.cutmix_size, self.cutmix_ratio), h, w, dev)
             perm = torch.randperm(nu).to(torch.int32).to(dev, non_blocking=True)  # a permutation by construction: taken as it is
-            ops.cutmix_perm(strong, perm, mask, out=net_in[lb + v * nu:lb + (v + 1) * nu])
+            ops.cutmix_perm(strong, perm, mask, out=net_in[first + v * nu:first + (v + 1) * nu])
             masks.append(mask)
             perms.append(perm)
-        net_in[:lb] = image[:lb]
-        out = self.model(net_in)
+        if fp:
+            net_in[:first] = image
+            out = self.model(net_in, fp_rows=(lb, nu), fp_drop=self.fp_drop)
+            code, self.last_kept = ops.w2s_labels(out[lb:first].detach(), self.dyn)
+        else:
+            net_in[:lb] = image[:lb]
+            out = self.model(net_in)
         sup = self.supervised_loss(out[:lb], label[:lb])
         self.last_supervised = sup.detach()
         unsup = None
         for v in range(views):
-            term = self.w2s(out[lb + v * nu:lb + (v + 1) * nu], code, masks[v], perms[v], dyn=self.dyn)
+            term = self.w2s(out[first + v * nu:first + (v + 1) * nu], code, masks[v], perms[v], dyn=self.dyn)
             unsup = term if unsup is None else unsup + term
         if views > 1:
             unsup = unsup / views
+        if fp:
+            fp_term = self.fp_weight * self.w2s(out[rows:rows + nu], code, None, None, dyn=self.dyn)
+            unsup = (1.0 - self.fp_weight) * unsup + fp_term
+            self.last_fp = fp_term.detach()
         self.last_unsup, self.last_code = unsup.detach(), code
         self.last_masks, self.last_perms, self.last_net_in = masks, perms, net_in
         return sup + unsup
