@@ -1,7 +1,12 @@
 """GPU checks of the fold-trainer losses (csrc/seg_loss.hip): masked soft Dice + CE with an ignore label, the hard tp / fp / fn,
 and the radix-select top-k CE -- against the reference's recorded numbers (tests/golden/seg_losses.npz) and the float64
 restatement (tests/_seg_loss_ref.py).  Tolerances are the project's for the fused loss against its golden (test_gpu_ops.py):
-|dvalue| < 2e-6, gradient atol 2e-7."""
+|dvalue| < 2e-6, gradient atol 2e-7.
+
+These are the checks through the public classes, at one slab and k1 = 2, 3, 4.  The kernels' dispatch branches -- more than one
+slab, k1 = 1 .. 8, every refusal of the fast route, the loop exits, every grid-stride wrap, the radix select with ties, label
+decoding, grad_out -- are run through the C entry points by tests/test_gpu_seg_loss_branches.py, whose docstring opens with the
+branch map (kernel -> branch -> test id)."""
 import json
 import math
 import os

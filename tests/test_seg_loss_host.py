@@ -223,3 +223,140 @@ def test_header_declares_and_library_exports_the_entry_points():
     assert b"mia_seg_loss_fwd" in lib.mia_last_error()
     assert lib.mia_topk_ce_workspace(0) == 0 and lib.mia_topk_ce_workspace(100) > 100
     assert lib.mia_seg_loss_workspace(2, 3, 4) >= 2 * 4 * (5 * 3 + 2)
+
+
+# ------------------------------------------------------------------ what tests/test_gpu_seg_loss_branches.py builds on
+def _torch_nll(c):
+    """torch's own per-pixel weighted cross-entropy in float64, [B*HW]."""
+    x = torch.from_numpy(c["logits"])
+    w = None if c["weight"] is None else torch.tensor(c["weight"], dtype=torch.float64)
+    lab = torch.from_numpy(c["labels"])
+    ign = -100 if c["ignore"] is None else c["ignore"]
+    return torch.nn.functional.cross_entropy(x, lab, weight=w, ignore_index=ign, reduction="none").reshape(-1).numpy()
+
+
+def test_case_builders_and_pixel_nll_against_torch():
+    """The per-pixel nll of the restatement equals torch.nn.functional.cross_entropy(reduction="none") in float64, and the
+    builders' switches do what they say."""
+    seen = 0
+    for k1 in range(1, 9):
+        for ltype, ignore in (("int64", IGN), ("int64", -100), ("uint8", IGN), ("uint8", -100), ("int64", None)):
+            c = R.build_case(2, k1, 37, ignore=ignore, ltype=ltype, seed=k1, weighted=k1 % 2 == 0)
+            assert c["logits"].shape == (2, k1, 37) and np.array_equal(c["logits"], R.fp32(c["logits"]))
+            assert c["ignore"] == (None if (ltype == "uint8" and ignore == -100) else ignore)
+            n_ign = 0 if c["ignore"] is None else int((c["labels"] == c["ignore"]).sum())
+            assert (n_ign > 0) == (c["ignore"] is not None)
+            if ltype == "uint8":
+                assert c["labels"].min() >= 0 and c["labels"].max() <= 255
+            nll = R.pixel_nll(c["logits"], c["labels"], c["ignore"], c["weight"])
+            assert nll.shape == (2 * 37,)
+            np.testing.assert_allclose(nll, _torch_nll(c), rtol=0, atol=1e-13)
+            if c["ignore"] is not None:
+                assert not nll[c["labels"].reshape(-1) == c["ignore"]].any()
+            assert (R.pixel_nll_bound(c["logits"], c["labels"], c["ignore"], c["weight"]) >= 0).all()
+            seen += 1
+    assert seen == 40
+    c = R.build_case(3, 4, 50, ignore=IGN, all_ignored_image=1, absent_class=2, zero_weight_class=3)
+    assert (c["labels"][1] == IGN).all() and not (c["labels"] == 2).any() and (c["labels"] == 3).any()
+    assert c["weight"][3] == 0.0 and c["weight"][:3] == [float(np.float32(v)) for v in R.CLASS_WEIGHTS[:3]]
+    assert R.CLASS_WEIGHTS[:4] == tuple(WEIGHTS[4])
+    # the same seed gives the same case; another seed another
+    d = R.build_case(3, 4, 50, ignore=IGN, all_ignored_image=1, absent_class=2, zero_weight_class=3)
+    assert np.array_equal(c["logits"], d["logits"]) and np.array_equal(c["labels"], d["labels"])
+    assert not np.array_equal(c["logits"], R.build_case(3, 4, 50, ignore=IGN, seed=1)["logits"])
+
+
+def test_select_check_and_topk_against_torch_topk():
+    """select_check on the fp32 bit patterns of a tie-free nll picks torch.topk's n-th value with r = m = 1, the restatement's top-k
+    value is the mean of torch.topk's values, and ties are counted as the definitions say."""
+    for name, c in R.topk_free_cases().items():
+        nll = R.pixel_nll(c["logits"], c["labels"], c["ignore"], c["weight"])
+        n = c["n_top"]
+        top = torch.topk(torch.from_numpy(nll), n).values
+        want = R.topk_ce(c["logits"], c["labels"], 100.0 * (n + 0.5) / nll.size, ignore=c["ignore"], weight=c["weight"])
+        assert want["n"] == n and want["n_eq"] == 1 and abs(want["loss"] - top.mean().item()) < 1e-12 * max(1.0, top.mean().item())
+        assert want["tau"] == top[-1].item()
+        n32 = nll.astype(np.float32)  # rounding to fp32 moves a value by less than its bound: still no tie at the threshold
+        tau, r, m = R.select_check(n32.view(np.uint32), n)
+        assert (r, m) == (1, 1), name
+        assert tau == int(torch.topk(torch.from_numpy(n32), n).values[-1].numpy().view(np.uint32)), name
+    bits = np.array([5, 9, 9, 9, 2, 0, 0, 7], dtype=np.uint32)
+    assert R.select_check(bits, 1) == (9, 1, 3) and R.select_check(bits, 3) == (9, 3, 3)
+    assert R.select_check(bits, 4) == (7, 1, 1) and R.select_check(bits, 7) == (0, 1, 2) and R.select_check(bits, 8) == (0, 2, 2)
+    assert R.select_check(np.array([0x3F800000, 0x3F800001], dtype=np.uint32), 1) == (0x3F800001, 1, 1)
+
+
+def test_rank_gap_of_every_tie_free_case():
+    """Asserted from float64 alone: with every pixel's nll moved by its bound the selection stays the same, so the device's fp32
+    selection must equal the restatement's -- no case needs to be filtered at run time."""
+    cases = dict(R.topk_free_cases())
+    for name, (nb, hw, n_above, frac) in {"wrap-fwd": (2, 524288 + 515, 150000, 0.2), "wrap-bwd": (2, 1048576 + 1029, 200000, 0.0)}.items():
+        cases[name] = R.gap_case(nb, hw, n_above, frac_ignored=frac)
+    for ltype in ("int64", "uint8"):
+        cases[f"labels-{ltype}"] = dict(R.label_case(ltype), n_top=R.LABEL_CASE_N_TOP)
+    cases["public-128x132"] = dict(R.build_case(3, 3, 128 * 132, ignore=IGN, seed=4), n_top=int(3 * 128 * 132 * 10 / 100))
+    for name, c in cases.items():
+        nll = R.pixel_nll(c["logits"], c["labels"], c["ignore"], c["weight"])
+        bound = R.pixel_nll_bound(c["logits"], c["labels"], c["ignore"], c["weight"])
+        margin = R.selection_margin(nll, bound, c["n_top"])
+        print(f"{name}: n_top {c['n_top']} of {nll.size}, max bound {bound.max():.2e}, margin {margin:.2e}")
+        assert margin > 0, name
+        assert np.sort(nll)[nll.size - c["n_top"]] > 1e-3, name  # and the threshold is not a zero (an ignored pixel)
+    # the span case does span many exponents, so that the first radix pass (sign + 7 exponent bits) already splits the values
+    c = cases["span"]
+    nll = R.pixel_nll(c["logits"], c["labels"], c["ignore"], c["weight"]).astype(np.float32)
+    assert np.unique(nll[nll > 0].view(np.uint32) >> 24).size >= 8
+    # weight0: the zero-weight class is present and none of its pixels is selected
+    c = cases["weight0"]
+    assert c["weight"][2] == 0.0 and (c["labels"] == 2).any()
+
+
+def test_tie_builder_claims_against_a_sort():
+    for (m, r), kw in R.TIE_CASES.items():
+        for k1 in (2, 3, 8):
+            c = R.tie_case(m, r, k1=k1, **kw)
+            nll = R.pixel_nll(c["logits"], c["labels"])
+            bound = R.pixel_nll_bound(c["logits"], c["labels"])
+            n = c["n_top"]
+            tau = np.sort(nll)[nll.size - n]
+            n_gt, n_eq = int((nll > tau).sum()), int((nll == tau).sum())
+            assert (n_gt, n_eq, n - n_gt) == (c["n_gt"], m, r) == (kw["n_a"], c["m"], c["r"])
+            assert np.array_equal(nll == tau, c["tied"]) and abs(tau - np.log(np.exp(1.5) + k1 - 1)) < 1e-12
+            # the tied pixels are copies of one pixel, bit for bit
+            t = np.flatnonzero(c["tied"])
+            flat = c["logits"].transpose(0, 2, 1).reshape(-1, k1)
+            assert (flat[t] == flat[t[0]]).all() and (c["labels"].reshape(-1)[t] == 1).all()
+            # A stays above T and B below it by more than the bounds; A's losses are distinct
+            a, b = nll > tau, nll < tau
+            assert (nll[a] - bound[a]).min() > tau + bound[t[0]] and (nll[b] + bound[b]).max() < tau - bound[t[0]]
+            assert np.unique(nll[a]).size == n_gt and nll[a].min() > 2.9
+            assert R.selection_margin(nll, bound, n, tied=c["tied"]) > 0
+            # T is spread over the images and over the 256-pixel blocks
+            hw = c["labels"].shape[1]
+            assert np.unique(t // hw).size == min(m, c["labels"].shape[0])
+            assert np.unique(t // 256).size >= min(m, nll.size // 256)
+            want = R.topk_ce(c["logits"], c["labels"], 100.0 * (n + 0.5) / nll.size)
+            assert (want["n"], want["n_gt"], want["n_eq"]) == (n, n_gt, m)
+
+
+def test_dense_ramp_precondition():
+    """Every valid pixel's float64 nll lies in [1 + 2^-10, 1 + 2^-7 - 2^-10]: 2^-10 inside the range [1, 1 + 2^-7) whose fp32
+    patterns share their upper 16 bits, a margin of 9.8e-4 against a per-pixel bound below 1e-6; and the steps of the ramp exceed
+    twice that bound, so the selection is defined."""
+    c = R.dense_ramp()
+    nll = R.pixel_nll(c["logits"], c["labels"], c["ignore"])
+    bound = R.pixel_nll_bound(c["logits"], c["labels"], c["ignore"])
+    valid = c["labels"].reshape(-1) != IGN
+    assert valid.sum() == c["n_valid"] and 0.75 * nll.size < c["n_valid"] < 0.85 * nll.size
+    tol = 1e-7  # the logits were rounded to fp32: d moves by 2^-25 relative, the nll by less than 4e-8
+    assert nll[valid].min() >= R.RAMP_LO - tol and nll[valid].max() <= R.RAMP_HI + tol and bound.max() < 1e-6
+    assert 2.0 ** -10 > 500 * bound.max()
+    pat = nll[valid].astype(np.float32).view(np.uint32)
+    assert np.unique(pat >> 16).tolist() == [0x3F80] and np.unique(pat).size == pat.size
+    assert np.unique((pat >> 8) & 0xFF).size > 100  # pass 2 has work to do, and pass 3 after it
+    assert np.diff(np.sort(nll[valid])).min() > 2 * bound.max()
+    assert R.selection_margin(nll, bound, c["n_top"]) > 0 and c["n_top"] == c["n_valid"] // 2
+    g = R.gap_case(2, 300, 40, frac_ignored=0.2)
+    gn = R.pixel_nll(g["logits"], g["labels"], g["ignore"])
+    assert (gn > 3.0).sum() == 40 and ((gn > 2.0) & (gn < 2.2)).sum() == 1 and (gn[(gn < 2.0)] < 0.98).all() and g["n_top"] == 41
+    assert 0.1 * 600 < (g["labels"] == IGN).sum() < 0.25 * 600
